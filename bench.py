@@ -13,12 +13,15 @@ the timed region; weights are random-init with randomised BN statistics.
 Protocol of ``value`` (SURVEY.md §8d = the reference's run.py:62-76): for each of the K timed frames
 ``synchronize(); network(batch); synchronize()`` on one stream with the default kernel variants — so
 ``value == 1 / latency_ms.mean`` — bracketed by a barrier + synchronize, MAX over ranks.  Rendering is frame-parallel
-(frame f -> rank f mod G, no data-path collective: scaling = weak; enerf_amd/frame_parallel.py).  Extra keys, never
-``value``: ``sequential_fps`` (same frames without the per-frame sync), ``pipelined_fps`` (frames in flight on several
-HIP streams with the throughput kernel options), ``sustained`` (>= 2000 frames).  Rank 0 prints ONE JSON line.
+(frame f -> rank f mod G, no data-path collective: scaling = weak; enerf_amd/frame_parallel.py).  Rank 0 prints ONE JSON
+line.  A plain run does only what that line's headline needs: set up, warm up, time ``--steps`` frames, print.  ``--full``
+adds the extra keys, never ``value``: ``sequential_fps`` (same frames without the per-frame sync), ``pipelined_fps``
+(frames in flight on several HIP streams with the throughput kernel options), ``sustained`` (>= 2000 frames), stage times
+and rooflines (live PMC), the lego / zju / training ``workloads``, CPU baselines and parity against the oracle.
+``--dump-outputs DIR`` writes what the last timed frame returned as ``DIR/<name>.npy``.
 
-``--gpus N`` with N > 1 and no ``WORLD_SIZE`` in the environment (a plain ``python bench.py --gpus 8``) re-executes itself
-under ``torch.distributed.run`` with N ranks on 127.0.0.1; a line whose ``n_gpus`` differs from ``--gpus`` is never printed.
+``--gpus N`` with N > 1 and no ``WORLD_SIZE`` in the environment (a plain ``python bench.py --gpus 8``) runs itself
+as a child under ``torch.distributed.run`` with N ranks on 127.0.0.1; a line whose ``n_gpus`` differs from ``--gpus`` is never printed.
 The timed frames rotate over ``--batches`` (default 4) distinct seeded batches, all resident in HBM before the timed region.
 """
 from __future__ import annotations
@@ -382,7 +385,7 @@ def train_child(timeout_s, live_pmc_ok=False, perceptual=False):
     line: ms_per_step, roofline of k_mlp_bwd, cpu_baseline of the oracle's train_step).  perceptual=True: the same step with the
     reference's full loss (the VGG16 term on, `bench.py --train`), 20 replays, ms_per_step only."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--train", "--steps", "20", "--warmup", "3"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--train", "--steps", "20", "--warmup", "3", "--full"]
     if perceptual:
         cmd += ["--no-stages", "--no-cpu-baseline", "--no-live-pmc"]
     else:
@@ -425,6 +428,26 @@ def make_workload(name, seed):
         return cfg, make_zju_batch(1024, 1024, 4, cfg, seed=rank), True, \
             "ZJU-MoCap CoreView_313 (zjumocap_eval.yaml at input_ratio 1.0: network_human, volume_planes 32,8, render_if False,True), 1024x1024, 4 src views, mask_at_box"
     raise SystemExit(f"unknown workload {name}")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every tensor of ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32.  Should the whole exceed
+    DUMP_LIMIT_BYTES, each array keeps a fixed, seeded sample of its flattened elements (sorted indices, the same for equal
+    shapes in every run), its share of the limit proportional to its size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    total = sum(a.nbytes for a in arrs.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrs)                      # (room for the .npy headers)
+    for k, a in arrs.items():
+        if total > budget:
+            n = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def emit_line(result):
@@ -538,7 +561,7 @@ def train_extras(args, net, batch, loss_fn, cfg, dev, ms_per_step):
         if not args.no_live_pmc and not args.emu:
             # HBM bytes of one launch, measured now: rocprofv3 --pmc passes over two EAGER steps of a child run (the same kernels
             # as the captured step; counters serialise the kernels either way)
-            flags = ["--train", "--train-eager", "--steps", "2", "--warmup", "1"] + (["--no-perceptual"] if args.no_perceptual else [])
+            flags = ["--train", "--train-eager", "--steps", "2", "--warmup", "1", "--full"] + (["--no-perceptual"] if args.no_perceptual else [])
             live = live_pmc([], kernel_prefix=f"k_mlp_bwd<{R}, {S}", child_flags=flags)       # (<R, S> or <R, S, level>)
             live = next(iter(live[""].values())) if live and live.get("") else None
             if live is not None:
@@ -689,8 +712,10 @@ def train_bench(args, rank, world, dev, dist, emu_lib=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:                                  # what the last step leaves a caller: its loss and the updated weights
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), **{f"param.{k}": v for k, v in net.named_parameters()}})
     extra = {}
-    if rank == 0 and not emu and not args.no_stages:
+    if args.full and rank == 0 and not emu and not args.no_stages:
         extra = train_extras(args, net, batch, loss_fn, cfg, dev, 1e3 * elapsed / args.steps)
     if dist is not None:
         dist.destroy_process_group()
@@ -753,6 +778,14 @@ def main():
     ap.add_argument("--emu", action="store_true",
                     help="launcher/CI check WITHOUT a GPU: run the same bench flow on the CPU lane emulator of the kernel "
                          "sources (tests/emu) over gloo with a 32x64 frame; the numbers mean nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: latency / sequential / sustained / pipelined legs, stage times, "
+                         "rooflines with live PMC, the torch FeatureNet and bf16x3 variants, the lego / zju / training workloads, "
+                         "CPU baselines and parity against the oracle (--train: the k_mlp_bwd roofline and the CPU step).  "
+                         "Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; inputs are seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
     t_process = time.perf_counter()
 
@@ -768,7 +801,9 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # a fresh child, never exec: device_count() above may already have opened the HIP runtime in this process
+        import subprocess
+        raise SystemExit(subprocess.run(cmd).returncode)
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -896,6 +931,12 @@ def main():
                 a, b = sum(recent[-20:-10]), sum(recent[-10:])
                 if abs(a - b) <= 0.015 * a or now - t_w > 2.0:
                     break
+        # the settled warm-up has no fixed length: a few more untimed frames bring the rotation back to batch 0, so the timed
+        # frames (and the last one, which --dump-outputs writes) see the same batches in every run with the same arguments
+        while frame_no[0] % nb:
+            step()
+            device_sync()
+            internal_warmup += 1
         device_sync()
         if dist is not None:
             # N > 1: the ranks leave their warm-ups at different moments, and the first to reach the timed region's barrier would idle
@@ -912,6 +953,8 @@ def main():
     finally:
         gc.enable()
     assert bool(torch.isfinite(out[f"rgb_level{last}"]).all()), "non-finite render"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     per_rank = [args.steps / t_rank]
     if dist is not None:                                # every rank's own rate next to the aggregate (reporting only)
         gathered = [None] * world
@@ -944,11 +987,11 @@ def main():
             result["vs_baseline_note"] = ("value / 21.78 FPS (README.md:121, one RTX 3090, the same per-frame-sync protocol); "
                                           "for N > 1 the numerator is the whole-job aggregate")
 
-    secondary = (rank == 0 and world == 1 and args.workload == "dtu" and not args.no_stages and not args.no_secondary
+    secondary = (args.full and rank == 0 and world == 1 and args.workload == "dtu" and not args.no_stages and not args.no_secondary
                  and not args.graph and not args.emu and args.feature_backend == "hip" and not opt_fields)
     pmc_all = None
-    # ---- extras on rank 0 (not in the timed region) ----
-    if rank == 0 and not args.no_stages and not args.graph:
+    # ---- extras on rank 0 (not in the timed region; --full only) ----
+    if args.full and rank == 0 and not args.no_stages and not args.graph:
         t0 = time.perf_counter()                      # host-side enqueue cost (no device sync inside)
         for _ in range(50):
             step()
@@ -1187,7 +1230,7 @@ def main():
         result["workloads"] = wl
 
     # ---- CPU baseline: the oracle (torch CPU restatement of the reference) on this box's host cores + parity ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import enerf_oracle as O
         from enerf_amd.synth import make_batch
         # torch CPU ops stop scaling (and regress) far below 256 threads: 8 threads rendered a DTU frame in 8.2 s in the

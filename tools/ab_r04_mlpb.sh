@@ -9,7 +9,7 @@ cp $R/enerf_amd/libenerf_hip.so /tmp/lib_keep3.so
 cd $R
 for v in "$@"; do
   cp $R/enerf_amd/_ab/lib_$v.so $R/enerf_amd/libenerf_hip.so
-  timeout 600 python bench.py --train --no-perceptual --steps 10 --warmup 2 --no-cpu-baseline > $O/$v.json 2> $O/$v.err
+  timeout 600 python bench.py --train --no-perceptual --steps 10 --warmup 2 --no-cpu-baseline --full > $O/$v.json 2> $O/$v.err
   python - <<PY
 import json
 try:

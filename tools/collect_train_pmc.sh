@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 TAG=${1:-rXX}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_${TAG}_train; mkdir -p $O
 cd /tmp
-PB="python $R/bench.py --train --train-eager --no-perceptual --steps 2 --warmup 1 --no-cpu-baseline --no-live-pmc"
+PB="python $R/bench.py --train --train-eager --no-perceptual --steps 2 --warmup 1 --no-cpu-baseline --no-live-pmc --full"
 i=0
 for ctr in "SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do

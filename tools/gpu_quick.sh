@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 TAG=${1:-r03_q}; shift; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q "$@" > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $O/pytest_gpu.log
-timeout 600 python bench.py > $O/bench_dtu.json 2> $O/bench_dtu.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/bench_dtu.json 2> $O/bench_dtu.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench_dtu.json").read().strip().splitlines()[-1])

@@ -1,5 +1,5 @@
 export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out/r05_run3; mkdir -p $O
-for i in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_$i.json 2> $O/bench_default_$i.err; python - <<PY
+for i in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default_$i.json 2> $O/bench_default_$i.err; python - <<PY
 import json
 d=json.loads(open("$O/bench_default_$i.json").read().strip().splitlines()[-1])
 w=d["workloads"]

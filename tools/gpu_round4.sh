@@ -10,6 +10,6 @@ bash tools/collect_profiles.sh ${TAG}_dtu dtu 1
 bash tools/collect_profiles.sh ${TAG}_lego lego 1
 bash tools/collect_profiles.sh ${TAG}_zju zju 1
 cd $R
-timeout 600 python bench.py --train --steps 20 --warmup 3 > $O/$TAG/train_bench.json 2> $O/$TAG/train_bench.err; tail -c 400 $O/$TAG/train_bench.json; echo
-timeout 600 python bench.py --train --no-perceptual --steps 20 --warmup 3 > $O/$TAG/train_bench_noperc.json 2> $O/$TAG/train_bench_noperc.err; tail -c 400 $O/$TAG/train_bench_noperc.json; echo
+timeout 600 python bench.py --train --steps 20 --warmup 3 --full > $O/$TAG/train_bench.json 2> $O/$TAG/train_bench.err; tail -c 400 $O/$TAG/train_bench.json; echo
+timeout 600 python bench.py --train --no-perceptual --steps 20 --warmup 3 --full > $O/$TAG/train_bench_noperc.json 2> $O/$TAG/train_bench_noperc.err; tail -c 400 $O/$TAG/train_bench_noperc.json; echo
 bash tools/gpu_train_stats.sh $TAG/train --no-perceptual > $O/$TAG/train_stats.log 2>&1; head -4 $O/$TAG/train_stats.log

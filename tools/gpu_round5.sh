@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 TAG=$1; K=$2; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 T0=$(date +%s.%N)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 echo "bench wall $(python -c "import time; print(round(time.time() - $T0, 1))") s"; tail -3 $O/bench_default.err
 python - <<PY
 import json

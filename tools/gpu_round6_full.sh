@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 TAG=${1:-r06_run2}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O/$TAG
 cd $R
 T0=$(date +%s.%N)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/$TAG/bench_default.json 2> $O/$TAG/bench_default.err; echo "bench rc=$?"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/$TAG/bench_default.json 2> $O/$TAG/bench_default.err; echo "bench rc=$?"
 echo "bench wall $(python -c "import time; print(round(time.time() - $T0, 1))") s"
 timeout 1800 python -m pytest tests -m gpu -q > $O/$TAG/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $O/$TAG/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/$TAG/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/$TAG/smoke.log
