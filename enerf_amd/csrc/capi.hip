@@ -24,9 +24,17 @@ void zero_async2(void* p, size_t bytes_p, void* q, size_t bytes_q, hipStream_t s
     zero_async(p, bytes_p, st);
     zero_async(q, bytes_q, st);
 }
+#ifdef ENERF_EMU
+// emulator build only (tests): the CU count the launch geometry is sized by, settable so that the persistent kernels' later passes
+// run on CPU too (tests/emu_lib.py emu_cu_count); not part of the C ABI, absent from the product library
+static int g_emu_cu_count = 256;
+}  // namespace enerf
+extern "C" void emu_set_cu_count(int n) { enerf::g_emu_cu_count = n > 0 ? n : 256; }
+namespace enerf {
+#endif
 int device_cu_count() {
 #ifdef ENERF_EMU
-    return 256;
+    return g_emu_cu_count;
 #else
     static int cached[64];                         // per device ordinal; 0 = not queried yet (benign race: same value)
     int dev = 0;

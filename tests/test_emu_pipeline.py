@@ -36,6 +36,15 @@ def test_emulated_kernels_match_reference_goldens(name):
         _close(v.numpy(), gold["out/" + k], 2e-5, k)
 
 
+@pytest.mark.parametrize("name", ["tiny_s3", "tiny_s4_mask"])
+def test_emulated_kernels_match_reference_goldens_on_one_cu(name):
+    """The same frames with the emulated library sized for one CU: the render kernel's persistent waves stride over several ray
+    tiles each, and the b4 convolutions take the variant chosen for a small device (a fresh Network: workspaces follow the count)."""
+    from emu_lib import emu_cu_count
+    with emu_cu_count(emu_lib(), 1):
+        test_emulated_kernels_match_reference_goldens(name)
+
+
 def test_render_precision_variants_match_reference_goldens():
     """enerf_options_t.render_precision: default = exact fp32 MFMAs; 2 = bf16x3 (every operand as two bf16 pieces on the bf16
     matrix cores, ~1e-5), 3 = bf16x6 (three pieces: fp32-level accuracy): all against the reference's outputs; bf16x6 must be

@@ -189,6 +189,37 @@ def _check_gather_bwd_tiled(lib, dev):
             assert _rel(o, r) < 2e-5, (Hr, Wr, Ns, Fc, wild, permute, name, _rel(o, r))
 
 
+CHANNEL_SUMS_CASES = ((1000, 8), (4099, 16), (777, 32), (1, 64), (30000, 4))
+
+
+def _channel_sums_passes(lib, n, Cc):
+    """Grid-stride passes of enerf_channel_sums' blocks over n positions: the launch has one partial row per block."""
+    blocks = int(lib.dll.enerf_channel_sums_workspace_bytes(n, Cc)) // (2 * Cc * 8)
+    return -(-(-(-n // (256 // (Cc // 4) * 16))) // blocks)
+
+
+def _check_channel_sums(lib, dev, g):
+    """BatchNorm statistics: enerf_channel_sums with scratch (partial rows + finish launch) and without (fp64 atomics) against
+    float64 sums."""
+    for n, Cc in CHANNEL_SUMS_CASES:
+        a_, b_, z_ = (torch.randn(n, Cc, generator=g).to(dev) for _ in range(3))
+        ms, mh = torch.rand(Cc, generator=g).to(dev) + 0.5, torch.randn(Cc, generator=g).to(dev) * 0.1
+        for args in ((a_, a_, None, None, None), (a_, b_, None, None, None), (a_, b_, z_, ms, mh)):
+            new = lib.channel_sums_raw(*args).cpu()
+            old = torch.empty((2, Cc), dtype=torch.float64, device=dev)
+            p_ = lambda t: None if t is None else t.data_ptr()
+            lib._check(lib.dll.enerf_channel_sums(p_(args[0]), p_(args[1]), p_(args[2]), p_(args[3]), p_(args[4]), n, Cc, old.data_ptr(),
+                                                  lib.stream_of(a_)), "channel_sums")
+            old = old.cpu()
+            m = (z_.cpu().double() * ms.cpu().double() + mh.cpu().double() > 0) if args[2] is not None else torch.ones(n, Cc, dtype=torch.bool)
+            # (the kernels evaluate the mask in fp32: build the reference from the same comparison)
+            if args[2] is not None:
+                m = (z_.cpu() * ms.cpu() + mh.cpu()) > 0
+            ref = torch.stack([(args[0].cpu().double() * m).sum(0), (args[0].cpu().double() * m * args[1].cpu().double()).sum(0)])
+            scale = float(ref.abs().max()) + 1e-30
+            assert float((new - ref).abs().max()) <= 1e-12 * scale * n and float((old - ref).abs().max()) <= 1e-12 * scale * n, (n, Cc)
+
+
 def _check_round4_kernel_pairs(lib, dev):
     """Round-4 kernel pairs that must agree with the form they replace.
     * the warp kernel with two depth planes per wave (even D) and the one-plane kernel (odd D): the same planes, bit for bit;
@@ -208,24 +239,7 @@ def _check_round4_kernel_pairs(lib, dev):
         v6 = lib.build_feature_volume(feat.to(dev), P.to(dev), dv6.to(dev), Cc).cpu()
         v5 = lib.build_feature_volume(feat.to(dev), P.to(dev), dv6[:, :5].contiguous().to(dev), Cc).cpu()
         assert torch.equal(v6[:, :5], v5), Cc
-    # ---- BatchNorm statistics: scratch form vs atomic form ----
-    for n, Cc in ((1000, 8), (4099, 16), (777, 32), (1, 64), (30000, 4)):
-        a_, b_, z_ = (torch.randn(n, Cc, generator=g).to(dev) for _ in range(3))
-        ms, mh = torch.rand(Cc, generator=g).to(dev) + 0.5, torch.randn(Cc, generator=g).to(dev) * 0.1
-        for args in ((a_, a_, None, None, None), (a_, b_, None, None, None), (a_, b_, z_, ms, mh)):
-            new = lib.channel_sums_raw(*args).cpu()
-            old = torch.empty((2, Cc), dtype=torch.float64, device=dev)
-            p_ = lambda t: None if t is None else t.data_ptr()
-            lib._check(lib.dll.enerf_channel_sums(p_(args[0]), p_(args[1]), p_(args[2]), p_(args[3]), p_(args[4]), n, Cc, old.data_ptr(),
-                                                  lib.stream_of(a_)), "channel_sums")
-            old = old.cpu()
-            m = (z_.cpu().double() * ms.cpu().double() + mh.cpu().double() > 0) if args[2] is not None else torch.ones(n, Cc, dtype=torch.bool)
-            # (the kernels evaluate the mask in fp32: build the reference from the same comparison)
-            if args[2] is not None:
-                m = (z_.cpu() * ms.cpu() + mh.cpu()) > 0
-            ref = torch.stack([(args[0].cpu().double() * m).sum(0), (args[0].cpu().double() * m * args[1].cpu().double()).sum(0)])
-            scale = float(ref.abs().max()) + 1e-30
-            assert float((new - ref).abs().max()) <= 1e-12 * scale * n and float((old - ref).abs().max()) <= 1e-12 * scale * n, (n, Cc)
+    _check_channel_sums(lib, dev, g)
     # ---- gather forward: B * P = 2 * 77 points (three waves, the middle one straddles the batch elements, the last is ragged) ----
     Hr, Wr, Fc = 12, 20, 11
     cfg1 = EnerfConfig().with_cas(render_scale=(1.0, 1.0))
@@ -254,6 +268,18 @@ CHECKS = [_check_round4_kernel_pairs, _check_gather_bwd_tiled, _check_s2k5_dgrad
 def test_train_glue_emulated(check):
     from emu_lib import emu_lib
     check(emu_lib(), torch.device("cpu"))
+
+
+def test_channel_sums_with_several_passes_per_block_emulated():
+    """The channel sums again with the emulated library sized for one CU (two blocks): every block strides over several chunks of
+    positions, and the partial rows add up what each block accumulated across its passes."""
+    from emu_lib import emu_cu_count, emu_lib
+    lib = emu_lib()
+    with emu_cu_count(lib, 1):
+        passes = {c: _channel_sums_passes(lib, *c) for c in CHANNEL_SUMS_CASES}
+        print("[channel_sums] passes per block at 1 CU:", passes)
+        assert passes[(4099, 16)] == 3 and passes[(30000, 4)] == 4, passes
+        _check_channel_sums(lib, torch.device("cpu"), torch.Generator().manual_seed(21))
 
 
 @pytest.mark.gpu

@@ -717,6 +717,15 @@ def test_conv_wgrad_emulated():
     _check_conv_wgrad(emu_lib(), torch.device("cpu"))
 
 
+def test_conv_wgrad_with_few_cus_emulated():
+    """The same weight-gradient checks with the emulated library sized for three CUs: the wgrad kernels' persistent tile loops
+    take several passes, chunk counts drop to 1, and the deferred second stages (k_wgrad_reduce_batch) add more partial rows each."""
+    from emu_lib import emu_cu_count, emu_lib
+    lib = emu_lib()
+    with emu_cu_count(lib, 3):
+        _check_conv_wgrad(lib, torch.device("cpu"))
+
+
 def test_hip_backward_stages_emulated():
     from emu_lib import emu_lib
     _check_hip_backward_stages(emu_lib(), torch.device("cpu"))

@@ -25,29 +25,39 @@ def _resize_ac(x, scale, recompute=None):
 
 
 
-def agg_forward(m, x):
+def _layer(seq, inp, pre=None):
+    """seq[0] (Linear), then the activation seq[1] if there is one; ``pre`` (a list): append (pre-activation, |W| |inp| + |b|) —
+    the second term scales the rounding error of the first, so a caller can tell where a ReLU gate is decided by rounding."""
+    z = seq[0](inp)
+    if pre is not None:
+        pre.append((z, F.linear(inp.abs(), seq[0].weight.abs(), seq[0].bias.abs())))
+    return seq[1](z) if len(seq) > 1 else z
+
+
+def agg_forward(m, x, pre=None):
     """Agg (nerf.py:74-89): x (B,P,S,F+4) -> (B,P,16)."""
     Fc = m.feat_ch
     S = x.shape[-2]
     a = x[..., :Fc]
     if hasattr(m, "view_fc"):
-        a = a + m.view_fc(x[..., Fc:])
+        a = a + _layer(m.view_fc, x[..., Fc:], pre)
     var = torch.var(a, dim=-2, keepdim=True).expand(-1, -1, S, -1)            # unbiased (nerf.py:82)
     avg = torch.mean(a, dim=-2, keepdim=True).expand(-1, -1, S, -1)
-    g = m.global_fc(torch.cat([a, var, avg], -1))
-    w = F.softmax(m.agg_w_fc(g), dim=-2)
-    return m.fc((g * w).sum(-2))
+    g = _layer(m.global_fc, torch.cat([a, var, avg], -1), pre)
+    w = F.softmax(_layer(m.agg_w_fc, g, pre), dim=-2)
+    return _layer(m.fc, (g * w).sum(-2), pre)
 
 
-def nerf_forward(m, vox, x):
-    """NeRF (nerf.py:29-43): vox (B,P,8), x (B,P,S,F+4) -> (B,P,4) = [rgb, sigma]."""
+def nerf_forward(m, vox, x, pre=None):
+    """NeRF (nerf.py:29-43): vox (B,P,8), x (B,P,S,F+4) -> (B,P,4) = [rgb, sigma].  ``pre``: a list that collects every ReLU
+    layer's pre-activations (see _layer)."""
     S = x.shape[2]
-    im = agg_forward(m.agg, x)
+    im = agg_forward(m.agg, x, pre)
     vi = torch.cat([vox, im], -1)
-    h = m.lr0(vi)
+    h = _layer(m.lr0, vi, pre)
     sigma = m.sigma(h)
     y = torch.cat([h, vi], -1).unsqueeze(2).expand(-1, -1, S, -1)
-    c = m.color(torch.cat([y, x], -1))
+    c = _layer(m.color[2:], _layer(m.color[:2], torch.cat([y, x], -1), pre), pre)
     cw = F.softmax(c, dim=-2)
     col = torch.sum(x[..., -7:-4] * cw, dim=-2)
     return torch.cat([col, sigma], -1)
