@@ -504,6 +504,38 @@ int enerf_eval_stats(const float* pred_rgb, const float* gt_rgb, const void* mas
                       n_depth, acc, (hipStream_t)stream);
     return check_launch("eval_stats");
 }
+static int eval_ssim_check_shape(int mask_elem_bytes, int mask_mode, int has_mask, int B, int img_h, int img_w, int rect_mode,
+                                 int crop_h, int crop_w) {
+    REQUIRE(B > 0 && img_h > 0 && img_w > 0, "eval_ssim: bad arguments (B, img_h, img_w must be positive)");
+    REQUIRE(mask_mode == ENERF_SSIM_MASK_GE1 || mask_mode == ENERF_SSIM_MASK_EQ1, "eval_ssim: mask_mode must be 0 (>= 1) or 1 (== 1)");
+    REQUIRE(rect_mode == ENERF_SSIM_RECT_NONE || rect_mode == ENERF_SSIM_RECT_CROP || rect_mode == ENERF_SSIM_RECT_BBOX,
+            "eval_ssim: rect_mode must be 0 (whole image), 1 (centre crop) or 2 (mask bounding box)");
+    if (has_mask) REQUIRE(mask_elem_bytes == 1 || mask_elem_bytes == 4, "eval_ssim: mask must be uint8/bool or int32");
+    REQUIRE(has_mask || rect_mode != ENERF_SSIM_RECT_BBOX, "eval_ssim: the bounding-box rectangle needs a mask");
+    REQUIRE(img_h >= 7 && img_w >= 7, "eval_ssim: unsupported image extent %dx%d: the 7x7 window exceeds it", img_h, img_w);
+    if (rect_mode == ENERF_SSIM_RECT_CROP) {
+        REQUIRE(crop_h >= 0 && crop_w >= 0, "eval_ssim: negative crop");
+        REQUIRE(img_h - 2LL * crop_h >= 7 && img_w - 2LL * crop_w >= 7,
+                "eval_ssim: unsupported crop (%d,%d) of a %dx%d image: the 7x7 window exceeds what is left", crop_h, crop_w,
+                img_h, img_w);
+    }
+    return ENERF_OK;
+}
+size_t enerf_eval_ssim_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int crop_h, int crop_w) {
+    if (eval_ssim_check_shape(1, 0, 1, B, img_h, img_w, rect_mode, crop_h, crop_w) != ENERF_OK) return 0;
+    return eval_ssim_workspace_bytes(B, img_h, img_w, rect_mode, crop_h, crop_w);
+}
+int enerf_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes, int mask_mode, int B,
+                    int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
+                    enerf_stream_t stream) {
+    REQUIRE(pred_rgb && gt_rgb && workspace && out, "eval_ssim: null pointer");
+    REQUIRE(((size_t)workspace & 7) == 0 && ((size_t)out & 7) == 0, "eval_ssim: workspace and out must be 8-byte aligned");
+    const int rc = eval_ssim_check_shape(mask_elem_bytes, mask_mode, mask != nullptr, B, img_h, img_w, rect_mode, crop_h, crop_w);
+    if (rc != ENERF_OK) return rc;
+    launch_eval_ssim(pred_rgb, gt_rgb, mask, mask_elem_bytes, mask_mode, B, img_h, img_w, rect_mode, crop_h, crop_w, workspace,
+                     out, (hipStream_t)stream);
+    return check_launch("eval_ssim");
+}
 int enerf_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                       enerf_stream_t stream) {
     REQUIRE(tar_ext && tar_ixt && xy && rays && B > 0 && N >= 0 && scale > 0.f, "gen_rays_at: bad arguments");

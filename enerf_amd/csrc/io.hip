@@ -2,8 +2,9 @@
 //   before: full-image ray generation (lib/datasets/enerf_utils.py:61-71, numpy on the host today; 10.5 MB of
 //           rays_1 per 512x640 frame would otherwise cross PCIe every frame)
 //   after:  uint8 packing + vertical flip for presentation (gui_human.py:88-91) and the evaluator's masked
-//           PSNR / depth statistics (lib/evaluators/enerf.py:67-71, 88-103) without a D2H copy of fp32 images.
-// All HBM-bound, one thread per output element.
+//           PSNR / depth statistics (lib/evaluators/enerf.py:67-71, 88-103) and SSIM (:76, enerf_human.py:54-66) without a
+//           D2H copy of fp32 images.
+// All HBM-bound, one thread per output element — except the SSIM kernels at the end (LDS tiles, float64 window sums).
 #include "kernels.h"
 
 namespace enerf {
@@ -281,6 +282,204 @@ void launch_eval_stats(const float* pred_rgb, const float* gt_rgb, const void* m
     unsigned grid = (unsigned)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024);
     ENERF_LAUNCH(k_eval_stats, grid, 256, 0, st, pred_rgb, gt_rgb, (const unsigned char*)mask, mask_bytes, n_rgb, img_w, img_h,
                  crop_h, crop_w, pred_depth, gt_depth, n_depth, acc);
+}
+
+// -------------------------------------------------------------------------------------------------
+// Evaluator SSIM (evaluators/enerf.py:67-69,76 and enerf_human.py:54-56,64-66): what
+// skimage.metrics.structural_similarity(gt, pred, multichannel=True) returns for float32 images — per channel, float64,
+// 7x7 uniform window, sample covariance (49/48), data_range 2 (C1 = 4e-4, C2 = 3.6e-3), mean over the windows that lie
+// wholly inside the image, mean over the channels.  The image is the rectangle (eval_center crop, or the bounding box of
+// the selected mask pixels) with gt and pred zeroed where the mask is off; both are applied while staging, nothing is copied.
+//
+// Channels are interleaved, so a row of the rectangle is a flat run of 3*rw floats in which the window's horizontal
+// neighbours sit 3 floats apart: the kernel works on flat columns and never separates the channels (the three channel means
+// have the same window count, so their mean is the sum over all flat columns / (3 * windows)).
+//
+// Tile: 256 flat output columns x 8 output rows per 256-thread block, one flat column per thread.  Staged: (8+6) rows x
+// (256+18) floats of both images = 2 * 14 * 274 * 4 B = 30,688 B of LDS -> 5 blocks (20 waves) per CU, so one block's staging
+// loads overlap another's arithmetic; 512 blocks at 512x640.  The halo makes a block read 14/8 * 274/256 = 1.87x its share of the
+// image, the excess out of L2 (the tile above staged the same rows).  Measured on MI355X against 16-row tiles (48 KB, 3 blocks per
+// CU, one block per CU at 512x640): 16.4 vs 20.1 us per call at 512x640, 37.5 vs 39.8 us at 1024x1024 with the box.
+// Each thread walks down its column: per staged row the five 7-tap horizontal sums (x, y, xx, yy, xy) in float64 from 14
+// conflict-free 4-byte LDS reads (lanes read consecutive floats), kept in a 7-deep register ring (35 doubles); every row from the
+// seventh on adds the ring up (the vertical 7 taps) and forms S.  No 8-byte partial sums go through LDS at all.  One partial per
+// block; k_ssim_finish adds them in a fixed order.
+// -------------------------------------------------------------------------------------------------
+constexpr int kSsimTH = 8, kSsimTF = 256;
+constexpr int kSsimRows = kSsimTH + 6, kSsimPitch = kSsimTF + 18;
+
+struct SsimRect { int y0, x0, rh, rw; };
+// box (rect_mode 2): {min x - W, min y - H, -max x - 1, -max y - 1} of the selected pixels, all 0 = none selected: every entry is
+// an atomicMin target that starts from a zero fill
+__device__ __forceinline__ SsimRect ssim_rect(int rect_mode, int img_h, int img_w, int crop_h, int crop_w, const int* box) {
+    SsimRect R = {0, 0, img_h, img_w};
+    if (rect_mode == 1) { R.y0 = crop_h; R.x0 = crop_w; R.rh = img_h - 2 * crop_h; R.rw = img_w - 2 * crop_w; }
+    if (rect_mode == 2) {
+        const int x0 = box[0] + img_w, y0 = box[1] + img_h, x1 = -box[2] - 1, y1 = -box[3] - 1;
+        R.y0 = y0; R.x0 = x0; R.rh = y1 - y0 + 1; R.rw = x1 - x0 + 1;
+        if (box[0] == 0) { R.y0 = 0; R.x0 = 0; R.rh = 0; R.rw = 0; }
+    }
+    return R;
+}
+// mask_mode 0: value >= 1 (evaluators/enerf.py:48), 1: value == 1 (enerf_human.py:54)
+__device__ __forceinline__ bool ssim_mask_on(const unsigned char* mask, int mask_bytes, int mask_mode, long long i) {
+    const int v = mask_bytes == 4 ? reinterpret_cast<const int*>(mask)[i] : (int)mask[i];
+    return mask_mode ? v == 1 : v >= 1;
+}
+
+// cv2.boundingRect(mask) (enerf_human.py:64) on the device: grid (blocks, B), box (B,4) zeroed by the caller.  A block takes whole
+// rows (no division per pixel), reduces to four values and sends at most four atomics, none where the box already covers its own
+// (a stale read only errs towards sending one: the entries only ever decrease).
+__global__ __launch_bounds__(256) void k_mask_bbox(const unsigned char* __restrict__ mask, int mask_bytes, int mask_mode,
+                                                   int img_h, int img_w, int* box) {
+    __shared__ int wmin[4][4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int m[4] = {0, 0, 0, 0};
+    for (int y = blockIdx.x; y < img_h; y += gridDim.x) {
+        const long long row = ((long long)b * img_h + y) * img_w;
+        for (int x = tid; x < img_w; x += 256)
+            if (ssim_mask_on(mask, mask_bytes, mask_mode, row + x)) {
+                m[0] = min(m[0], x - img_w); m[1] = min(m[1], y - img_h); m[2] = min(m[2], -x - 1); m[3] = min(m[3], -y - 1);
+            }
+    }
+    for (int k = 0; k < 4; ++k) {
+        for (int s = 32; s >= 1; s >>= 1) m[k] = min(m[k], __shfl_xor(m[k], s));
+        if ((tid & 63) == 0) wmin[tid >> 6][k] = m[k];
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const int v = min(min(wmin[0][tid], wmin[1][tid]), min(wmin[2][tid], wmin[3][tid]));
+        if (v != 0 && box[b * 4 + tid] > v) atomicMin(box + b * 4 + tid, v);
+    }
+}
+
+// S of one window and channel from its five 49-term sums {x, y, xx, yy, xy} (_structural_similarity.py:188-208).  No fma
+// contraction: identical images must give A1 == B1 and A2 == B2 bit for bit, hence S == 1.0 exactly.
+__device__ __forceinline__ double ssim_window(double sx, double sy, double sxx, double syy, double sxy) {
+#ifndef ENERF_EMU
+#pragma clang fp contract(off)
+#endif
+    const double inv = 1.0 / 49.0, cov = 49.0 / 48.0;
+    const double C1 = (0.01 * 2.0) * (0.01 * 2.0), C2 = (0.03 * 2.0) * (0.03 * 2.0);
+    const double ux = sx * inv, uy = sy * inv, uxx = sxx * inv, uyy = syy * inv, uxy = sxy * inv;
+    const double vx = cov * (uxx - ux * ux), vy = cov * (uyy - uy * uy), vxy = cov * (uxy - ux * uy);
+    const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
+    const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
+    return (A1 * A2) / (B1 * B2);
+}
+
+// grid (flat-column tiles, row tiles, B); partial (B, gridDim.x * gridDim.y): every block writes its own entry (0 when its
+// tile lies outside the rectangle, which in rect_mode 2 only the device knows)
+__global__ __launch_bounds__(256) void k_ssim_moments(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                      const unsigned char* __restrict__ mask, int mask_bytes, int mask_mode,
+                                                      int img_h, int img_w, int rect_mode, int crop_h, int crop_w,
+                                                      const int* __restrict__ box, double* __restrict__ partial) {
+    __shared__ float lx[kSsimRows * kSsimPitch], ly[kSsimRows * kSsimPitch];
+    __shared__ double wsum[4];
+    const int tid = threadIdx.x, b = blockIdx.z;
+    double* out = partial + (long long)b * (gridDim.x * gridDim.y) + (blockIdx.y * gridDim.x + blockIdx.x);
+    const SsimRect R = ssim_rect(rect_mode, img_h, img_w, crop_h, crop_w, box + b * 4);
+    const int oy0 = blockIdx.y * kSsimTH, of0 = blockIdx.x * kSsimTF;       // first output row / flat column of the tile
+    const int out_h = R.rh - 6, out_f = (R.rw - 6) * 3, in_f = R.rw * 3;
+    if (oy0 >= out_h || of0 >= out_f) {                                     // block-uniform (also: rectangle under 7x7)
+        if (tid == 0) *out = 0.0;
+        return;
+    }
+    const long long img0 = (long long)b * img_h * img_w;
+    // a fixed trip count, unrolled, and the three loads of an element independent of each other (the mask selects afterwards): the
+    // loads of several elements are in flight together instead of one memory round trip after the other
+    constexpr int kStage = (kSsimRows * kSsimPitch + 255) / 256;
+#pragma unroll 8
+    for (int it = 0; it < kStage; ++it) {
+        const int e = it * 256 + tid;
+        const int r = e / kSsimPitch, f = e - r * kSsimPitch;
+        const int ry = oy0 + r, rf = of0 + f;                               // row / flat column inside the rectangle
+        float vx = 0.f, vy = 0.f;
+        if (r < kSsimRows && ry < R.rh && rf < in_f) {
+            const int px = rf / 3;
+            const long long pix = img0 + (long long)(R.y0 + ry) * img_w + (R.x0 + px);
+            const bool on = mask == nullptr || ssim_mask_on(mask, mask_bytes, mask_mode, pix);   // gt[mask == False] = 0 (:68-69)
+            const float gx = gt[pix * 3 + (rf - px * 3)], gy = pred[pix * 3 + (rf - px * 3)];
+            vx = on ? gx : 0.f;
+            vy = on ? gy : 0.f;
+        }
+        if (r < kSsimRows) { lx[e] = vx; ly[e] = vy; }
+    }
+    __syncthreads();
+    const bool col_on = of0 + tid < out_f;
+    double h[7][5];
+    double acc = 0.0;
+#pragma unroll
+    for (int r = 0; r < kSsimRows; ++r) {
+        const float* px = lx + r * kSsimPitch + tid;
+        const float* py = ly + r * kSsimPitch + tid;
+        double s[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {                                       // products of two fp32 values: exact in fp64
+            const double x = (double)px[3 * t], y = (double)py[3 * t];
+            s[0] += x; s[1] += y; s[2] += x * x; s[3] += y * y; s[4] += x * y;
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) h[r % 7][k] = s[k];
+        if (r >= 6) {
+            double m[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) m[k] = ((h[0][k] + h[1][k]) + (h[2][k] + h[3][k])) + ((h[4][k] + h[5][k]) + h[6][k]);
+            const double S = ssim_window(m[0], m[1], m[2], m[3], m[4]);
+            if (col_on && oy0 + (r - 6) < out_h) acc += S;
+        }
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) *out = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// one block per image: the partials in a fixed order (strided per thread, butterfly per wave, the four waves in order), then
+// out[b] = {mean S, windows per channel}; a rectangle under 7x7 (empty or tiny bounding box): {NaN, 0}
+__global__ __launch_bounds__(256) void k_ssim_finish(const double* __restrict__ partial, int nblk, int img_h, int img_w,
+                                                     int rect_mode, int crop_h, int crop_w, const int* __restrict__ box,
+                                                     double* __restrict__ out) {
+    __shared__ double wsum[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    double a = 0.0;
+    for (int i = tid; i < nblk; i += 256) a += partial[(long long)b * nblk + i];
+    a = wave_sum(a);
+    if ((tid & 63) == 0) wsum[tid >> 6] = a;
+    __syncthreads();
+    if (tid != 0) return;
+    const SsimRect R = ssim_rect(rect_mode, img_h, img_w, crop_h, crop_w, box + b * 4);
+    const bool ok = R.rh >= 7 && R.rw >= 7;
+    const double n = ok ? (double)(R.rh - 6) * (double)(R.rw - 6) : 0.0;
+    out[2 * b] = ok ? ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) / (3.0 * n) : NAN;
+    out[2 * b + 1] = n;
+}
+
+static void ssim_grid(int img_h, int img_w, int rect_mode, int crop_h, int crop_w, int* tiles_f, int* tiles_y) {
+    const int rh = rect_mode == 1 ? img_h - 2 * crop_h : img_h, rw = rect_mode == 1 ? img_w - 2 * crop_w : img_w;
+    *tiles_f = cdiv((rw - 6) * 3, kSsimTF);
+    *tiles_y = cdiv(rh - 6, kSsimTH);
+}
+size_t eval_ssim_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int crop_h, int crop_w) {
+    int tf, ty;
+    ssim_grid(img_h, img_w, rect_mode, crop_h, crop_w, &tf, &ty);
+    return (size_t)B * 16 + (size_t)B * tf * ty * sizeof(double);          // boxes (B,4) int32 | partials (B, tiles) double
+}
+void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_bytes, int mask_mode, int B,
+                      int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
+                      hipStream_t st) {
+    int tf, ty;
+    ssim_grid(img_h, img_w, rect_mode, crop_h, crop_w, &tf, &ty);
+    int* box = (int*)workspace;
+    double* partial = (double*)((char*)workspace + (size_t)B * 16);
+    if (rect_mode == 2) {
+        zero_async(box, (size_t)B * 16, st);
+        ENERF_LAUNCH(k_mask_bbox, dim3((unsigned)(img_h < 512 ? img_h : 512), (unsigned)B), 256, 0, st, (const unsigned char*)mask,
+                     mask_bytes, mask_mode, img_h, img_w, box);
+    }
+    ENERF_LAUNCH(k_ssim_moments, dim3((unsigned)tf, (unsigned)ty, (unsigned)B), 256, 0, st, pred_rgb, gt_rgb,
+                 (const unsigned char*)mask, mask_bytes, mask_mode, img_h, img_w, rect_mode, crop_h, crop_w, box, partial);
+    ENERF_LAUNCH(k_ssim_finish, (unsigned)B, 256, 0, st, partial, tf * ty, img_h, img_w, rect_mode, crop_h, crop_w, box, out);
 }
 
 }  // namespace enerf

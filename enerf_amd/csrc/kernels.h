@@ -159,6 +159,11 @@ void launch_pack_rgb8(const float* rgb, int H, int W, int flip, unsigned char* o
 void launch_eval_stats(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_bytes, long long n_rgb,
                        int img_w, int img_h, int crop_h, int crop_w, const float* pred_depth, const float* gt_depth,
                        long long n_depth, double* acc, hipStream_t st);
+// SSIM of the evaluators (skimage's structural_similarity on the cropped / boxed, mask-zeroed images); workspace: boxes | partials
+size_t eval_ssim_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int crop_h, int crop_w);
+void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_bytes, int mask_mode, int B,
+                      int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
+                      hipStream_t st);
 void launch_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                         hipStream_t st);
 void launch_rays_bbox_mask(const float* rays, const float* bounds, long long n, int* mask, hipStream_t st);

@@ -3,7 +3,11 @@
 Mirrors the part of ``lib/evaluators/enerf.py`` the hot path can serve: masked / centre-cropped PSNR per rendered level
 (:45-71) and the NeRF / MVS depth statistics (:88-103), same ``evaluate(output, batch)`` / ``summarize()`` surface, so
 ``run.py:69-70`` can call it in place of the skimage/numpy evaluator.  The reductions run in ``enerf_eval_stats`` (io.hip):
-one 48-byte D2H copy per (frame, level) instead of the fp32 images.  SSIM and LPIPS stay where they are (skimage / lpips).
+one 48-byte D2H copy per (frame, level) instead of the fp32 images.  With ``eval_ssim=True`` the evaluators' second number, SSIM
+(:76: skimage's ``structural_similarity(gt, pred, multichannel=True)`` on the mask-zeroed, centre-cropped images), comes from
+``enerf_eval_ssim`` in the same way and the copy grows to 64 bytes.  ``DeviceEvaluatorHuman`` is the counterpart of
+``lib/evaluators/enerf_human.py`` (``mask_at_box`` at the last level, SSIM on the mask's bounding rectangle).  LPIPS stays where
+it is (the lpips package and its VGG weights).
 """
 from __future__ import annotations
 
@@ -12,7 +16,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .config import EnerfConfig
-from .lib import EnerfLib, get_lib
+from .lib import EnerfLib, get_lib, stats_from_acc
 
 
 def nearest_resize_index(src: int, dst: int, device) -> torch.Tensor:
@@ -25,14 +29,16 @@ def nearest_resize_index(src: int, dst: int, device) -> torch.Tensor:
 
 class DeviceEvaluator:
     def __init__(self, cfg: EnerfConfig, eval_center: bool = False, eval_depth: bool = False,
-                 lib: Optional[EnerfLib] = None):
-        self.cfg, self.eval_center, self.eval_depth = cfg, eval_center, eval_depth
+                 lib: Optional[EnerfLib] = None, eval_ssim: bool = False):
+        self.cfg, self.eval_center, self.eval_depth, self.eval_ssim = cfg, eval_center, eval_depth, eval_ssim
         self._lib = lib
         self.reset()
 
     def reset(self):
         self.psnrs: List[float] = []
         self.level_psnrs: Dict[int, List[float]] = {}
+        self.ssims: List[float] = []
+        self.level_ssims: Dict[int, List[float]] = {}
         self.abs, self.acc_2, self.acc_10 = [], [], []
         self.mvs_abs, self.mvs_acc_2, self.mvs_acc_10 = [], [], []
 
@@ -60,7 +66,10 @@ class DeviceEvaluator:
                 if self.eval_depth and last and "tar_dpt" in batch:
                     depth_args = dict(pred_depth=output[f"depth_level{i}"][b].contiguous(),
                                       gt_depth=batch["tar_dpt"][b].reshape(-1).contiguous())
-                st = self.lib.eval_stats(pred, gt, mask, image_hw=(h, w), crop=crop, **depth_args)
+                if self.eval_ssim:
+                    st = self._stats_and_ssim(i, last, pred, gt, mask, (h, w), crop, depth_args)
+                else:
+                    st = self.lib.eval_stats(pred, gt, mask, image_hw=(h, w), crop=crop, **depth_args)
                 self.level_psnrs.setdefault(i, []).append(st["psnr"])
                 if last:
                     self.psnrs.append(st["psnr"])
@@ -79,13 +88,55 @@ class DeviceEvaluator:
                         if ms:
                             self.mvs_abs.append(ms["abs"]); self.mvs_acc_2.append(ms["acc_2"]); self.mvs_acc_10.append(ms["acc_10"])
 
+    def _stats_and_ssim(self, level, last, pred, gt, mask, hw, crop, depth_args, bbox=False, mask_is_one=False) -> dict:
+        """psnr / depth accumulator and SSIM of one image: two enqueued calls, ONE blocking 64-byte D2H copy for both."""
+        acc = self.lib.eval_stats(pred, gt, mask, image_hw=hw, crop=crop, sync=False, **depth_args)
+        ss = self.lib.eval_ssim(pred, gt, mask, image_hw=hw, crop=crop, bbox=bbox, mask_is_one=mask_is_one, sync=False)
+        both = torch.cat([acc, ss.reshape(-1)]).cpu().tolist()
+        self.level_ssims.setdefault(level, []).append(both[6])
+        if last:
+            self.ssims.append(both[6])
+        return stats_from_acc(both[:6])
+
     def summarize(self) -> dict:
         mean = lambda v: sum(v) / len(v) if v else float("nan")
         ret = {"psnr": mean(self.psnrs)}
         ret.update({f"psnr_level{i}": mean(v) for i, v in self.level_psnrs.items()})
+        if self.eval_ssim:
+            ret["ssim"] = mean(self.ssims)
+            ret.update({f"ssim_level{i}": mean(v) for i, v in self.level_ssims.items()})
         if self.abs:
             ret.update(abs=mean(self.abs), acc_2=mean(self.acc_2), acc_10=mean(self.acc_10))
         if self.mvs_abs:                 # the reference accumulates these (:101-103) but never prints them; reported here
             ret.update(mvs_abs=mean(self.mvs_abs), mvs_acc_2=mean(self.mvs_acc_2), mvs_acc_10=mean(self.mvs_acc_10))
         self.reset()
         return ret
+
+
+class DeviceEvaluatorHuman(DeviceEvaluator):
+    """``lib/evaluators/enerf_human.py:29-84`` on the device: the mask is ``mask_at_box`` at the last cascade level and all ones
+    at the others (:39-42), selected by ``== 1`` (:54); psnr over the selected pixels (:58); SSIM on the selected pixels'
+    bounding rectangle with everything else zeroed (:55-56,64-66).  The rectangle is found on the device.  ``summarize()``
+    returns ``psnr``, ``ssim`` (last level) and both per rendered level; no depth statistics, as in the reference."""
+
+    def __init__(self, cfg: EnerfConfig, lib: Optional[EnerfLib] = None):
+        super().__init__(cfg, eval_center=False, eval_depth=False, lib=lib, eval_ssim=True)
+
+    def evaluate(self, output: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]):
+        cas = self.cfg.cas
+        B, S, _, H, W = batch["src_inps"].shape
+        for i in range(cas.num):
+            if not cas.render_if[i]:
+                continue
+            h, w = int(H * cas.render_scale[i]), int(W * cas.render_scale[i])
+            last = i == cas.num - 1
+            for b in range(B):
+                pred = output[f"rgb_level{i}"][b].reshape(h * w, 3).contiguous()
+                gt = batch[f"rgb_{i}"][b].reshape(h * w, 3).contiguous()
+                mask = None
+                if last:                                                # any dtype the dataset hands over; == 1 decided here
+                    mask = (batch["mask_at_box"][b].reshape(h * w) == 1).to(torch.uint8)
+                st = self._stats_and_ssim(i, last, pred, gt, mask, (h, w), (0, 0), {}, bbox=mask is not None, mask_is_one=True)
+                self.level_psnrs.setdefault(i, []).append(st["psnr"])
+                if last:
+                    self.psnrs.append(st["psnr"])

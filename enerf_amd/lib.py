@@ -226,6 +226,8 @@ _SIGNATURES = {
     "enerf_gen_rays": (_i, [_f, _f, _i, _i, _i, _fl, _f, _f]),
     "enerf_pack_rgb8": (_i, [_f, _i, _i, _i, _f, _f]),
     "enerf_eval_stats": (_i, [_f, _f, C.c_void_p, _i, _ll, _i, _i, _i, _i, _f, _f, _ll, _f, _f]),
+    "enerf_eval_ssim_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "enerf_eval_ssim": (_i, [_f, _f, C.c_void_p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_void_p, C.c_void_p, _f]),
     "enerf_gen_rays_at": (_i, [_f, _f, C.c_void_p, _i, _i, _fl, _f, _f]),
     "enerf_rays_bbox_mask": (_i, [_f, _f, _ll, C.c_void_p, _f]),
     "enerf_select_views": (_i, [_f, _i, _f, _i, C.c_void_p, _f]),
@@ -1138,6 +1140,39 @@ class EnerfLib:
             return acc
         return stats_from_acc(acc.cpu().tolist())
 
+    def eval_ssim(self, pred_rgb, gt_rgb, mask=None, image_hw=None, crop=(0, 0), bbox=False, mask_is_one=False, sync=True):
+        """``ssim(gt, pred, multichannel=True)`` of evaluators/enerf.py:76 / enerf_human.py:66 (skimage 0.18: float64, 7x7 uniform
+        window, data_range 2) on device, with the evaluators' preprocessing: pixels whose ``mask`` is off (``>= 1`` is on; ``== 1``
+        with ``mask_is_one``) count as 0, and the image is the ``eval_center`` slice ``crop`` = (crop_h, crop_w) or, with ``bbox``,
+        the bounding box of the on pixels.  ``pred_rgb`` / ``gt_rgb``: (B, h*w, 3) or (h*w, 3) with ``image_hw`` = (h, w); ``mask``
+        (B, h*w).  Returns one float per image (NaN: empty or < 7 pixel bounding box) after ONE 16*B-byte D2H copy — or, with
+        ``sync=False``, the (B,2) float64 device tensor {ssim, windows per channel}; nothing synchronises then."""
+        if image_hw is None:
+            raise EnerfError("eval_ssim needs image_hw=(h, w)")
+        h, w = int(image_hw[0]), int(image_hw[1])
+        if h <= 0 or w <= 0 or pred_rgb.numel() == 0 or pred_rgb.numel() % (h * w * 3) or gt_rgb.numel() != pred_rgb.numel():
+            raise EnerfError(f"eval_ssim: pred / gt must be (B, {h}*{w}, 3) tensors of the same size")
+        B = pred_rgb.numel() // (h * w * 3)
+        mb = 0
+        if mask is not None:
+            if mask.dtype not in (torch.int32, torch.uint8, torch.bool) or not mask.is_contiguous():
+                raise EnerfError("mask must be a contiguous int32 / uint8 / bool tensor")
+            if mask.numel() != B * h * w:
+                raise EnerfError(f"eval_ssim: mask has {mask.numel()} elements, the images {B * h * w} pixels")
+            mb = mask.element_size()
+        rect = 2 if bbox else (1 if (int(crop[0]), int(crop[1])) != (0, 0) else 0)
+        ch, cw = (int(crop[0]), int(crop[1])) if rect == 1 else (0, 0)
+        pp, gp = _ptr(pred_rgb), _ptr(gt_rgb)                          # dtype / contiguity checked before anything is sized
+        nbytes = self.dll.enerf_eval_ssim_workspace_bytes(B, h, w, rect, ch, cw)
+        if nbytes == 0:
+            raise EnerfError(f"eval_ssim failed: {self.dll.enerf_last_error().decode()}")
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=pred_rgb.device)
+        out = torch.empty((B, 2), dtype=torch.float64, device=pred_rgb.device)
+        self._check(self.dll.enerf_eval_ssim(pp, gp, None if mask is None else mask.data_ptr(), mb, int(bool(mask_is_one)), B, h, w,
+                                             rect, ch, cw, ws.data_ptr(), out.data_ptr(), self.stream_of(pred_rgb)), "eval_ssim")
+        if not sync:
+            return out
+        return out.cpu()[:, 0].tolist()
 
     def depth_stats(self, pred_depth, gt_depth, sync=True):
         """The depth statistics alone (evaluators/enerf.py:96-103: abs / acc_2 / acc_10 over gt != 0): enerf_eval_stats with

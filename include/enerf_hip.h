@@ -619,6 +619,33 @@ int enerf_eval_stats(const float* pred_rgb, const float* gt_rgb, const void* mas
                      int img_w, int img_h, int crop_h, int crop_w, const float* pred_depth, const float* gt_depth,
                      long long n_depth, double* acc, enerf_stream_t stream);
 
+/* ---- evaluator SSIM on the device (ABI v11 grew by these two entries; new symbols only, the version number is unchanged) ----
+ * enerf_eval_ssim replaces `ssim(gt, pred, multichannel=True)` of lib/evaluators/enerf.py:76 and enerf_human.py:66 together with
+ * the preprocessing in front of it (enerf.py:48-54,67-69; enerf_human.py:39-42,54-56,64): what skimage 0.18's
+ * structural_similarity computes for float32 images — per channel, float64, 7x7 uniform window, sample covariance, data_range 2
+ * (C1 = 4e-4, C2 = 3.6e-3), mean over the windows wholly inside the image, mean over the three channels.
+ *   pred_rgb, gt_rgb  (B, img_h*img_w, 3) fp32;  mask (B, img_h*img_w) uint8/bool (mask_elem_bytes 1) or int32 (4), or NULL = all on
+ *   mask_mode         which pixels are ON: ENERF_SSIM_MASK_GE1 value >= 1 (enerf.py:48), ENERF_SSIM_MASK_EQ1 value == 1
+ *                     (enerf_human.py:54).  gt and pred count as 0 where the mask is off (zeroed BEFORE the filter).
+ *   rect_mode         the sub-image SSIM runs on: ENERF_SSIM_RECT_NONE the whole image; ENERF_SSIM_RECT_CROP the eval_center
+ *                     slice [crop_h:img_h-crop_h, crop_w:img_w-crop_w] (enerf.py:50-54; a crop of 0 keeps everything);
+ *                     ENERF_SSIM_RECT_BBOX cv2.boundingRect of the ON pixels (enerf_human.py:64), found on the device per image.
+ *   out               (B,2) doubles: {ssim, windows per channel = (rh-6)*(rw-6) of the rectangle}.  Bit-identical from call to
+ *                     call (no floating-point atomics; partial sums added in a fixed order).
+ *   workspace         enerf_eval_ssim_workspace_bytes(B, img_h, img_w, rect_mode, crop_h, crop_w) bytes, 8-byte aligned.
+ * An image or crop under 7 pixels in either extent is rejected before anything is launched (ENERF_EINVAL, "unsupported ...";
+ * skimage raises ValueError there; the size query returns 0).  A bounding box that is empty or under 7 pixels in either extent
+ * is known on the device only: that image's result is {NaN, 0}. */
+#define ENERF_SSIM_MASK_GE1 0
+#define ENERF_SSIM_MASK_EQ1 1
+#define ENERF_SSIM_RECT_NONE 0
+#define ENERF_SSIM_RECT_CROP 1
+#define ENERF_SSIM_RECT_BBOX 2
+size_t enerf_eval_ssim_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int crop_h, int crop_w);
+int enerf_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes, int mask_mode, int B,
+                    int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
+                    enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
