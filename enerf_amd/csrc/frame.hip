@@ -95,6 +95,61 @@ void launch_mask_compact(const void* mask, int elem_bytes, long long n, int* ind
 }
 
 // =====================================================================================================================
+// Source-view gather of a cached frame (enerf_forward_cached; the reference's per-camera gather, zjumocap/enerf_interactive.py:
+// 214-217, applied to what the FeatureNet made of the images instead of the images).  For every (b,s) slot of the frame the
+// selected view's blocks — one contiguous run per segment: a feature map or a texel image of that view — are copied from the
+// cache into the frame's workspace, and the two camera rows with them.  The view index is read here, on the device.
+// Pure HBM byte work: grid (x, B*S), a block walks its slot's segments with 16-byte loads and stores, four in flight per thread,
+// grid-stride in x.  An index outside [0,V) is never used as an address: the slot is filled with NaN instead.
+// =====================================================================================================================
+constexpr int kGatherSegs = 6;
+struct GatherSeg { const float4* src; float4* dst; long long n4; };    // n4: 16-byte words per view
+struct GatherJob {
+    GatherSeg seg[kGatherSegs];
+    int nseg, V;
+    const int* view_idx;                   // (B*S) on the device; nullptr = slot i takes view i (the cache build's camera copy)
+    const float *exts, *ixts;              // (V,16), (V,9)
+    float *dst_exts, *dst_ixts;            // (B*S,16), (B*S,9), or nullptr = no cameras in this launch
+};
+__global__ __launch_bounds__(256) void k_gather_sources(GatherJob J) {
+    const int img = blockIdx.y;
+    const int v = J.view_idx != nullptr ? J.view_idx[img] : img;
+    const bool ok = v >= 0 && v < J.V;
+    const float qnan = __int_as_float(0x7fc00000);
+    const long long stride = (long long)gridDim.x * 256;
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    for (int s = 0; s < J.nseg; ++s) {
+        const long long n4 = J.seg[s].n4;
+        float4* d = J.seg[s].dst + (long long)img * n4;
+        if (ok) {
+            const float4* p = J.seg[s].src + (long long)v * n4;
+            long long i = i0;
+            for (; i + 3 * stride < n4; i += 4 * stride) {
+                const float4 a = p[i], b = p[i + stride], c = p[i + 2 * stride], e = p[i + 3 * stride];
+                d[i] = a; d[i + stride] = b; d[i + 2 * stride] = c; d[i + 3 * stride] = e;
+            }
+            for (; i < n4; i += stride) d[i] = p[i];
+        } else {
+            const float4 n = make_float4(qnan, qnan, qnan, qnan);
+            for (long long i = i0; i < n4; i += stride) d[i] = n;
+        }
+    }
+    if (blockIdx.x == 0 && J.dst_exts != nullptr && threadIdx.x < 25) {
+        const int t = threadIdx.x;
+        if (t < 16) J.dst_exts[img * 16 + t] = ok ? J.exts[(long long)v * 16 + t] : qnan;
+        else J.dst_ixts[img * 9 + (t - 16)] = ok ? J.ixts[(long long)v * 9 + (t - 16)] : qnan;
+    }
+}
+void launch_gather_sources(const GatherJob& J, int n_img, hipStream_t st) {
+    long long most = 1;
+    for (int s = 0; s < J.nseg; ++s) most = J.seg[s].n4 > most ? J.seg[s].n4 : most;
+    long long gx = cdivl(most, 256 * 4), cap = (long long)device_cu_count() * 8 / n_img;
+    if (gx > cap) gx = cap;
+    if (gx < 1) gx = 1;
+    ENERF_LAUNCH_SIMPLE(k_gather_sources, dim3((unsigned)gx, (unsigned)n_img), 256, 0, st, J);
+}
+
+// =====================================================================================================================
 // Frame plan: shapes of every level and the carving of the caller's workspace.
 // =====================================================================================================================
 namespace {
@@ -106,40 +161,54 @@ struct LevelPlan {
     size_t proj, dv, nf, vol, feat3d, prob, depth, std, dmvs, tex, rays;
 };
 struct FramePlan {
-    int tex2, hip_feats;
+    int tex2, hip_feats, cached;
     size_t f[3], featnet_ws, featnet_ws_bytes, costreg_ws, costreg_ws_bytes;
+    size_t cam_exts, cam_ixts;                     // cached frame: the gathered (B,S,4,4) / (B,S,3,3) camera rows
     size_t ray_index, ray_count, mask_ws;          // float-sized slots
     LevelPlan L[ENERF_MAX_LEVELS];
     size_t total_floats;
 };
 inline int scaled(int n, double s) { return (int)((double)n * s); }      // python: int(H * scale)
 
-int make_plan(const enerf_frame_args_t* a, FramePlan* P) {
-    REQUIRE(a, "forward: null args");
-    const enerf_cascade_t& c = a->cas;
-    REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "forward: cas_config.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
-    REQUIRE(a->B > 0 && a->S >= 2 && a->S <= 4 && a->H > 0 && a->W > 0 && a->H % 4 == 0 && a->W % 4 == 0,
-            "forward: bad batch shape B=%d S=%d H=%d W=%d (S in 2..4, H and W divisible by 4)", a->B, a->S, a->H, a->W);
-    REQUIRE(a->src_inps && a->src_exts && a->src_ixts && a->tar_ext && a->tar_ixt && a->near_far, "forward: null batch tensor");
-    const int nf = (a->feats_nchw[0] != nullptr) + (a->feats_nchw[1] != nullptr) + (a->feats_nchw[2] != nullptr);
-    REQUIRE(nf == 0 || nf == 3, "forward: feats_nchw needs all three levels or none");
-    P->hip_feats = nf == 0;
-    if (P->hip_feats) REQUIRE(a->feature_net_packed, "forward: feature_net_packed missing");
-    // level_2 is only ever the im_feat of a full-resolution render: then the FeatureNet emits it as render texels
+// level_2 is only ever the im_feat of a full-resolution render: then the FeatureNet emits it as render texels
+int cascade_tex2(const enerf_cascade_t& c) {
     int uses = 0, all_full = 1;
     for (int i = 0; i < c.num; ++i)
         if (c.render_if[i] && c.render_im_feat_level[i] == 2) {
             ++uses;
             all_full &= (c.render_scale[i] == 1.0 && c.im_ibr_scale[i] == 1.0 && c.nerf_model_feat_ch[i] == 8);
         }
-    P->tex2 = P->hip_feats && uses > 0 && all_full && c.num <= 2;
+    return uses > 0 && all_full && c.num <= 2;
+}
+
+// cached: the frame's feature maps, texels and source cameras come from a source cache (enerf_forward_cached): no FeatureNet
+// scratch, camera slots instead; every other offset rule is enerf_forward's
+int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
+    REQUIRE(a, "forward: null args");
+    const enerf_cascade_t& c = a->cas;
+    P->cached = cached;
+    REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "forward: cas_config.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
+    REQUIRE(a->B > 0 && a->S >= 2 && a->S <= 4 && a->H > 0 && a->W > 0 && a->H % 4 == 0 && a->W % 4 == 0,
+            "forward: bad batch shape B=%d S=%d H=%d W=%d (S in 2..4, H and W divisible by 4)", a->B, a->S, a->H, a->W);
+    REQUIRE(a->tar_ext && a->tar_ixt && a->near_far, "forward: null batch tensor");
+    if (!cached) {
+        REQUIRE(a->src_inps && a->src_exts && a->src_ixts, "forward: null batch tensor");
+        const int nf = (a->feats_nchw[0] != nullptr) + (a->feats_nchw[1] != nullptr) + (a->feats_nchw[2] != nullptr);
+        REQUIRE(nf == 0 || nf == 3, "forward: feats_nchw needs all three levels or none");
+        P->hip_feats = nf == 0;
+        if (P->hip_feats) REQUIRE(a->feature_net_packed, "forward: feature_net_packed missing");
+    } else
+        P->hip_feats = 1;                              // the cache holds the HIP FeatureNet's channels-last maps
+    P->tex2 = P->hip_feats && cascade_tex2(c);
     size_t off = 0;
     auto take = [&](size_t nfloats) { size_t r = off; off += (nfloats + 63) / 64 * 64; return r; };   // 256-B aligned
     const long long n_img = (long long)a->B * a->S;
     const int fh[3] = {a->H / 4, a->H / 2, a->H}, fw[3] = {a->W / 4, a->W / 2, a->W}, fc[3] = {32, 16, 8};
     for (int l = 0; l < 3; ++l) P->f[l] = take((size_t)n_img * fh[l] * fw[l] * (l == 2 && P->tex2 ? 12 : fc[l]));
-    P->featnet_ws_bytes = P->hip_feats ? enerf_feature_net_workspace_bytes((int)n_img, a->H, a->W) : 0;
+    P->featnet_ws_bytes = P->hip_feats && !cached ? enerf_feature_net_workspace_bytes((int)n_img, a->H, a->W) : 0;
     P->featnet_ws = take(P->featnet_ws_bytes / sizeof(float));
+    P->cam_exts = P->cam_ixts = 0;
+    if (cached) { P->cam_exts = take((size_t)n_img * 16); P->cam_ixts = take((size_t)n_img * 9); }
     P->costreg_ws_bytes = 0;
     for (int i = 0; i < c.num; ++i) {
         LevelPlan& L = P->L[i];
@@ -278,10 +347,38 @@ size_t enerf_forward_workspace_bytes(const enerf_frame_args_t* a) {
     return P.total_floats * sizeof(float);
 }
 
-int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
+}  // extern "C"
+
+namespace {
+// what the host can see of a cache against the frame / cascade it is used with (enerf_forward_cached, enerf_source_cache_build)
+int check_cache(const char* what, const enerf_source_cache_t* k, const enerf_cascade_t& c, int H, int W) {
+    REQUIRE(k, "%s: null cache", what);
+    REQUIRE(k->V >= 1, "%s: cache has V=%d views", what, k->V);
+    REQUIRE(k->H == H && k->W == W, "%s: cache was built for %dx%d images, the frame has %dx%d", what, k->H, k->W, H, W);
+    const int l2s = cascade_tex2(c) ? 12 : 8;
+    REQUIRE(k->l2_stride == l2s, "%s: cache has l2_stride=%d, this cascade needs %d (a cache is valid for the cascade it was built for)",
+            what, k->l2_stride, l2s);
+    REQUIRE(k->feat_l0 && k->feat_l1 && k->feat_l2 && k->exts && k->ixts, "%s: null cache buffer", what);
+    size_t bits = (size_t)k->feat_l0 | (size_t)k->feat_l1 | (size_t)k->feat_l2 | (size_t)k->exts | (size_t)k->ixts;
+    for (int i = 0; i < c.num && i < ENERF_MAX_LEVELS; ++i) {
+        if (!c.render_if[i] || (c.render_im_feat_level[i] == 2 && l2s == 12)) continue;
+        REQUIRE(k->tex[i], "%s: cache has no texel image for rendered level %d", what, i);
+        bits |= (size_t)k->tex[i];
+    }
+    REQUIRE((bits & 15) == 0, "%s: cache buffers must be 16-byte aligned", what);
+    return ENERF_OK;
+}
+
+// The frame driver behind enerf_forward (cache == nullptr) and enerf_forward_cached.
+int run_frame(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
     FramePlan P;
-    int rc = make_plan(a, &P);
+    int rc = make_plan(a, &P, cache != nullptr);
     if (rc != ENERF_OK) return rc;
+    if (cache != nullptr) {
+        rc = check_cache("forward_cached", cache, a->cas, a->H, a->W);
+        if (rc != ENERF_OK) return rc;
+        REQUIRE(view_idx, "forward_cached: null view_idx (a (B,S) int32 device array)");
+    }
     REQUIRE(a->workspace, "forward: null workspace");
     if (a->workspace_bytes < P.total_floats * sizeof(float))
         return fail(ENERF_EWORKSPACE, "forward: workspace too small (%zu < %zu bytes)", a->workspace_bytes,
@@ -308,6 +405,9 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
             launch_mask_compact(a->mask_at_box, a->mask_elem_bytes, last.n_rays, ray_index, ray_count, ws + P.mask_ws, st);
     }
 
+    // the source cameras: the batch's, or (cached frame) the rows the gather leaves in the workspace
+    const float* src_exts = cache ? ws + P.cam_exts : a->src_exts;
+    const float* src_ixts = cache ? ws + P.cam_ixts : a->src_ixts;
     // ---- FeatureNet (feature_net.py:27-36) -> channels-last maps; level_2 straight to render texels when it can ----
     float* f[3] = {ws + P.f[0], ws + P.f[1], ws + P.f[2]};
     const int fh[3] = {a->H / 4, a->H / 2, a->H}, fw[3] = {a->W / 4, a->W / 2, a->W}, fc[3] = {32, 16, 8};
@@ -347,7 +447,7 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
 #ifndef ENERF_PREP_JOB
 #define ENERF_PREP_JOB 1             // 0 (A/B): the preparation as launches of its own inside the level loop (rounds 1 - 5)
 #endif
-    if (P.hip_feats && ENERF_PREP_JOB) {
+    if (P.hip_feats && ENERF_PREP_JOB && cache == nullptr) {
         const LevelPlan& L0 = P.L[0];
         job.near_far = a->near_far; job.dv = ws + L0.dv; job.nf = ws + L0.nf;
         job.B = a->B; job.D = L0.D; job.h = L0.h; job.w = L0.w; job.depth_inv = c.depth_inv[0];
@@ -356,7 +456,52 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
                                 (float)c.volume_scale[i]};
         job.nblocks = prep_job_blocks(a->B, L0.D, L0.h, L0.w, 256);
     }
-    if (P.hip_feats) {
+    if (cache != nullptr) {
+        // ---- cached frame: gather the selected views' maps, texels and cameras instead of computing them.  Level 0 / level 1 maps,
+        // the non-final levels' texels and the cameras (everything the chain needs first) on the caller's stream; the level-2 map
+        // and the last level's texels, two thirds of the bytes and needed only by the final render, on the side lane.  The camera-only
+        // preparation reads the gathered rows, so it runs as the level loop's own launches (prep_carried stays 0).
+        GatherJob main_job, side_job;
+        memset(&main_job, 0, sizeof(main_job));
+        memset(&side_job, 0, sizeof(side_job));
+        main_job.V = side_job.V = cache->V;
+        main_job.view_idx = side_job.view_idx = view_idx;
+        main_job.exts = cache->exts; main_job.ixts = cache->ixts;
+        main_job.dst_exts = ws + P.cam_exts; main_job.dst_ixts = ws + P.cam_ixts;
+        auto add = [](GatherJob& J, const float* src, float* dst, long long floats_per_view) {
+            J.seg[J.nseg++] = GatherSeg{reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), floats_per_view / 4};
+        };
+        add(main_job, cache->feat_l0, f[0], (long long)fh[0] * fw[0] * 32);
+        add(main_job, cache->feat_l1, f[1], (long long)fh[1] * fw[1] * 16);
+        bool uses2 = c.num >= 3;                      // level_2 feeds a third level's cost volume, or IS a render's texels (stride 12);
+        for (int i = 0; i < c.num; ++i)               // a render from the plain map reads its own texel image instead
+            uses2 = uses2 || (P.L[i].render && c.render_im_feat_level[i] == 2 && P.tex2);
+        if (uses2) add(side_job, cache->feat_l2, f[2], (long long)a->H * a->W * cache->l2_stride);
+        for (int i = 0; i < c.num; ++i) {
+            const LevelPlan& L = P.L[i];
+            if (!L.render || (c.render_im_feat_level[i] == 2 && P.tex2)) continue;
+            add(i + 1 < c.num ? main_job : side_job, cache->tex[i], ws + L.tex, (long long)L.Hr * L.Wr * 4 * ((L.F + 3) / 4));
+        }
+#ifndef ENERF_EMU
+        if (!(a->options && a->options->single_stream) && side_job.nseg > 0) lane = side_lane(st);
+        if (lane != nullptr) {
+            lane_busy = std::unique_lock<std::mutex>(lane->busy);
+            hipEventRecord(lane->trunk, st);           // the lane starts behind the previous frame and the producer of view_idx
+            hipStreamWaitEvent(lane->stream, lane->trunk, 0);
+            launch_gather_sources(main_job, n_img, st);
+            launch_gather_sources(side_job, n_img, lane->stream);
+            hipEventRecord(lane->l1, lane->stream);
+            hipEventRecord(lane->l2, lane->stream);
+            forked = true; joined[1] = 1; joined[2] = 0;       // (level 1 came with the caller's stream)
+        } else
+#endif
+        {
+            for (int s = 0; s < side_job.nseg; ++s) main_job.seg[main_job.nseg++] = side_job.seg[s];
+            launch_gather_sources(main_job, n_img, st);
+        }
+        rc = check_launch("forward_cached: gather");
+        if (rc != ENERF_OK) return bail(rc);
+    } else if (P.hip_feats) {
         const int l2s = P.tex2 ? 12 : 8;
         auto fstage = [&](int stage, enerf_stream_t s) {
             const bool first = stage == ENERF_FEAT_ALL || stage == ENERF_FEAT_TRUNK;
@@ -437,7 +582,7 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
         bool prep_done = false;
         if (pending_prob != nullptr) {
             // (the level's projection matrices are already there when the frame's first launch carried the preparation job)
-            prep_done = launch_regress_and_values(a->src_ixts, a->src_exts, a->tar_ixt, a->tar_ext, a->S, (float)c.im_feat_scale[i],
+            prep_done = launch_regress_and_values(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->S, (float)c.im_feat_scale[i],
                                                   (float)c.volume_scale[i], prep_carried && i < 3 ? nullptr : proj, pending_prob, pending_dv, pnf, pending_D, hp, wp,
                                                   pending_inv, const_cast<float*>(pdepth), const_cast<float*>(pstd), a->B, L.D,
                                                   L.h, L.w, c.depth_inv[i], dv, nf, st);
@@ -448,7 +593,7 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
         }
         if (i == 0 && prep_carried) prep_done = true;                  // level 0: planes + matrices came with the first launch
         if (!prep_done)
-            rc = enerf_level_prep(a->src_ixts, a->src_exts, a->tar_ixt, a->tar_ext, a->B, a->S, (float)c.im_feat_scale[i],
+            rc = enerf_level_prep(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->B, a->S, (float)c.im_feat_scale[i],
                                   (float)c.volume_scale[i], proj, a->near_far, pdepth, pstd, pnf, L.D, L.h, L.w, hp, wp,
                                   c.depth_inv[i], dv, nf, stream);
         else
@@ -495,7 +640,7 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
         const int fl = c.render_im_feat_level[i];
         const int TEX = 4 * ((L.F + 3) / 4);
         const float* tex;
-        need_level(fl);                                                // the texel source (joined here, inside the texel stage)
+        if (cache == nullptr || (fl == 2 && P.tex2)) need_level(fl);   // the texel source (joined here, inside the texel stage)
         // a non-final level's render is a leaf of the frame: fork it (its inputs are complete on the caller's stream here)
         bool render_forked = false;
         enerf_stream_t rs = stream;
@@ -508,7 +653,10 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
         }
 #endif
         if (fl == 2 && P.tex2) tex = f[2];
-        else {
+        else if (cache != nullptr) {                                   // gathered with the maps; the last level's on the side lane
+            if (i + 1 == c.num) need_level(2);
+            tex = ws + L.tex;
+        } else {
             float* t = ws + L.tex;
             if (P.hip_feats)
                 rc = enerf_pack_texels_cl(f[fl], fc[fl], a->src_inps, a->H, a->W, L.Hr, L.Wr, TEX, n_img, t, rs);
@@ -531,7 +679,7 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
         // ---- build_rays + render_rays (utils.py:390-420, network.py:24-43), one launch ----
         enerf_render_args_t ra;
         memset(&ra, 0, sizeof(ra));
-        ra.tex = tex; ra.vol = feat3d; ra.src_exts = a->src_exts; ra.src_ixts = a->src_ixts; ra.tar_ext = a->tar_ext;
+        ra.tex = tex; ra.vol = feat3d; ra.src_exts = src_exts; ra.src_ixts = src_ixts; ra.tar_ext = a->tar_ext;
         ra.packed = a->nerf_packed[i];
         ra.rgb = a->rgb[i]; ra.depth = a->depth[i]; ra.weights = a->weights[i];
         ra.B = a->B; ra.N = (int)L.n_rays; ra.S = a->S; ra.n_samples = L.Ns; ra.depth_inv = c.depth_inv[i];
@@ -564,6 +712,91 @@ int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) {
 #endif
     need_level(1); need_level(2);        // the caller's stream never returns ahead of the side lane
     return check_launch("forward");
+}
+}  // namespace
+
+extern "C" {
+
+int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) { return run_frame(a, nullptr, nullptr, stream); }
+
+size_t enerf_forward_cached_workspace_bytes(const enerf_frame_args_t* a, const enerf_source_cache_t* cache) {
+    FramePlan P;
+    if (make_plan(a, &P, true) != ENERF_OK) return 0;
+    if (check_cache("forward_cached", cache, a->cas, a->H, a->W) != ENERF_OK) return 0;
+    return P.total_floats * sizeof(float);
+}
+
+int enerf_forward_cached(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
+    REQUIRE(cache, "forward_cached: null cache");
+    return run_frame(a, cache, view_idx, stream);
+}
+
+// ---- the cache itself: sizes for a cascade, and the build (FeatureNet + texel packing over the V views, <= 4 at a time) ----
+int enerf_source_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, int* l2_stride, long long* floats) {
+    REQUIRE(cas && l2_stride && floats, "source_cache_sizes: null pointer");
+    const enerf_cascade_t& c = *cas;
+    REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "source_cache_sizes: cas_config.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
+    REQUIRE(V >= 1 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "source_cache_sizes: bad shape V=%d H=%d W=%d (H and W divisible by 4)", V, H, W);
+    const int l2s = cascade_tex2(c) ? 12 : 8;
+    const int fh[3] = {H / 4, H / 2, H}, fw[3] = {W / 4, W / 2, W}, fc[3] = {32, 16, 8};
+    *l2_stride = l2s;
+    for (int l = 0; l < 3; ++l) floats[l] = (long long)V * fh[l] * fw[l] * (l == 2 ? l2s : fc[l]);
+    for (int i = 0; i < ENERF_MAX_LEVELS; ++i) {
+        floats[3 + i] = 0;
+        if (i >= c.num || !c.render_if[i]) continue;
+        const int fl = c.render_im_feat_level[i];
+        REQUIRE(fl >= 0 && fl <= 2 && fc[fl] == c.nerf_model_feat_ch[i],
+                "source_cache_sizes: render_im_feat_level[%d]=%d does not have nerf_model_feat_ch=%d channels", i, fl, c.nerf_model_feat_ch[i]);
+        const int Hr = scaled(H, c.render_scale[i]), Wr = scaled(W, c.render_scale[i]);
+        REQUIRE(fh[fl] == Hr && fw[fl] == Wr, "source_cache_sizes: level %d renders at %dx%d but feature level_%d is %dx%d "
+                "(the HIP FeatureNet path needs render_scale == im_ibr_scale)", i, Hr, Wr, fl, fh[fl], fw[fl]);
+        if (fl == 2 && l2s == 12) continue;
+        floats[3 + i] = (long long)V * Hr * Wr * 4 * ((c.nerf_model_feat_ch[i] + 3 + 3) / 4);
+    }
+    floats[6] = (long long)V * 16;
+    floats[7] = (long long)V * 9;
+    return ENERF_OK;
+}
+
+size_t enerf_source_cache_build_workspace_bytes(int H, int W) { return enerf_feature_net_workspace_bytes(4, H, W); }
+
+int enerf_source_cache_build(const enerf_source_cache_t* cache, const float* src_inps, const float* exts, const float* ixts,
+                             const float* feature_net_packed, const enerf_cascade_t* cas, int chunk, void* workspace,
+                             size_t workspace_bytes, const enerf_options_t* options, enerf_stream_t stream) {
+    REQUIRE(cache && cas, "source_cache_build: null cache / cascade");
+    REQUIRE(src_inps && exts && ixts && feature_net_packed && workspace, "source_cache_build: null pointer");
+    if (chunk == 0) chunk = 4;
+    REQUIRE(chunk >= 1 && chunk <= 4, "source_cache_build: chunk=%d (1..4 images per FeatureNet call)", chunk);
+    const int V = cache->V, H = cache->H, W = cache->W;
+    long long floats[ENERF_SOURCE_CACHE_BUFFERS];
+    int l2s = 0;
+    int rc = enerf_source_cache_sizes(cas, V, H, W, &l2s, floats);
+    if (rc != ENERF_OK) return rc;
+    rc = check_cache("source_cache_build", cache, *cas, H, W);
+    if (rc != ENERF_OK) return rc;
+    if (workspace_bytes < enerf_source_cache_build_workspace_bytes(H, W))
+        return fail(ENERF_EWORKSPACE, "source_cache_build: workspace too small");
+    const int fh[3] = {H / 4, H / 2, H}, fw[3] = {W / 4, W / 2, W}, fc[3] = {32, 16, 8};
+    float* maps[3] = {cache->feat_l0, cache->feat_l1, cache->feat_l2};
+    for (int v0 = 0; v0 < V; v0 += chunk) {
+        const int n = V - v0 < chunk ? V - v0 : chunk;
+        const float* img = src_inps + (size_t)v0 * 3 * H * W;
+        float* m[3];
+        for (int l = 0; l < 3; ++l) m[l] = maps[l] + (size_t)v0 * fh[l] * fw[l] * (l == 2 ? l2s : fc[l]);
+        rc = enerf_feature_net(feature_net_packed, img, n, H, W, m[0], m[1], m[2], l2s, workspace, workspace_bytes, options, stream);
+        if (rc != ENERF_OK) return rc;
+        for (int i = 0; i < cas->num; ++i) {
+            if (floats[3 + i] == 0) continue;
+            const int fl = cas->render_im_feat_level[i], TEX = 4 * ((fc[fl] + 3 + 3) / 4);
+            rc = enerf_pack_texels_cl(m[fl], fc[fl], img, H, W, fh[fl], fw[fl], TEX, n, cache->tex[i] + (size_t)v0 * fh[fl] * fw[fl] * TEX, stream);
+            if (rc != ENERF_OK) return rc;
+        }
+    }
+    GatherJob J;                                        // the cameras: slot v takes view v
+    memset(&J, 0, sizeof(J));
+    J.V = V; J.exts = exts; J.ixts = ixts; J.dst_exts = cache->exts; J.dst_ixts = cache->ixts;
+    launch_gather_sources(J, V, (hipStream_t)stream);
+    return check_launch("source_cache_build");
 }
 
 }  // extern "C"

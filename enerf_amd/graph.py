@@ -4,6 +4,12 @@ ctypes/torch bookkeeping (0.26 ms of host time per 1.09 ms frame) — once, repl
     frame = GraphedFrame(net, example_batch)      # captures on a side stream; static input/output buffers
     out = frame(batch)                            # copies the batch into the static inputs, one hipGraphLaunch
 
+``fn`` (optional) is what gets captured instead of ``net`` itself: a callable ``fn(static_batch) -> dict`` around the network, e.g.
+the interactive loop ``select_views -> net.forward_cached -> pack_rgb8`` (nothing in it may synchronise).  Tensors of the batch may
+then also be changed in place between replays (a device-resident view index, the target camera).  The graph holds the addresses
+of whatever ``fn`` closed over: a SourceCache rebuilt at new addresses (a new time frame) is NOT noticed — the replay keeps reading
+the old one, which stays alive here — so either refill the same cache's buffers in place or capture again.
+
 The graph holds the shapes and the weights' packed images of the capture; re-capture after load_state_dict /
 a shape change.  Works because the HIP path never synchronises, allocates only through torch's (graph-aware)
 caching allocator and takes every pointer from tensors that stay alive inside the graph's private pool."""
@@ -15,25 +21,29 @@ import torch
 
 
 class GraphedFrame:
-    def __init__(self, net, batch: Dict[str, torch.Tensor], warmup: int = 2):
+    def __init__(self, net, batch: Dict[str, torch.Tensor], warmup: int = 2, fn=None):
         if net.training:
             raise RuntimeError("GraphedFrame: call net.eval() first")
         if getattr(net, "human", False) and not net.static_shapes:
             raise RuntimeError("GraphedFrame: the human variant needs static_shapes=True (no count readback inside a graph)")
         self.net = net
+        # kept for the life of the graph: the closure owns what the captured kernels read besides the network's own buffers
+        # (a SourceCache's maps live outside the graph's private pool)
+        self.fn = fn
+        run = net if fn is None else fn
         self.static_in = {k: v.clone() if torch.is_tensor(v) else v for k, v in batch.items()}
         with torch.no_grad():
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(max(1, warmup)):          # packs weights, sizes workspaces, warms the allocator
-                    net(self.static_in)
+                    run(self.static_in)
             torch.cuda.current_stream().wait_stream(s)
             self.graph = torch.cuda.CUDAGraph()
             # capture on the warm-up stream: the library's per-stream side lane (frame.hip) then exists before the capture
             # starts, and the lane's fork/join (event waits) is captured as a two-branch graph
             with torch.cuda.graph(self.graph, stream=s):
-                self.static_out = net(self.static_in)
+                self.static_out = run(self.static_in)
         # the graph holds raw addresses of the packed weight images and the FeatureNet scratch, which live OUTSIDE the
         # graph's private pool: keep them alive here and refuse to replay once the network has replaced them
         self._held = {k: v[0] for k, v in net._packed.items()}

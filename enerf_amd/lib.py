@@ -119,6 +119,15 @@ class FrameArgs(C.Structure):
                    ("stage_events", C.POINTER(C.c_void_p))])
 
 
+class SourceCacheStruct(C.Structure):
+    """``enerf_source_cache_t``."""
+    _fields_ = ([(n, _f) for n in ("feat_l0", "feat_l1", "feat_l2")] + [("tex", _fL), ("exts", _f), ("ixts", _f)]
+                + [(n, _i) for n in ("V", "H", "W", "l2_stride")])
+
+
+SOURCE_CACHE_BUFFERS = 5 + MAX_LEVELS
+
+
 def cascade_struct(cfg) -> Cascade:
     """EnerfConfig -> enerf_cascade_t."""
     cas = cfg.cas
@@ -232,6 +241,12 @@ _SIGNATURES = {
     "enerf_rays_bbox_mask": (_i, [_f, _f, _ll, C.c_void_p, _f]),
     "enerf_select_views": (_i, [_f, _i, _f, _i, C.c_void_p, _f]),
     "enerf_gather_views": (_i, [_f, _f, _f, C.c_void_p, _i, _i, _i, _f, _f, _f, _f]),
+    "enerf_source_cache_sizes": (_i, [C.POINTER(Cascade), _i, _i, _i, C.POINTER(_i), C.POINTER(_ll)]),
+    "enerf_source_cache_build_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "enerf_source_cache_build": (_i, [C.POINTER(SourceCacheStruct), _f, _f, _f, _f, C.POINTER(Cascade), _i, C.c_void_p, C.c_size_t,
+                                      C.POINTER(Options), _f]),
+    "enerf_forward_cached_workspace_bytes": (C.c_size_t, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct)]),
+    "enerf_forward_cached": (_i, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct), C.c_void_p, _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1067,6 +1082,32 @@ class EnerfLib:
 
     def forward(self, args: "FrameArgs", stream):
         self._check(self.dll.enerf_forward(C.byref(args), stream), "forward")
+
+    # -- source-view cache (enerf_amd/source_cache.py owns the tensors) -----------------------------------
+    def source_cache_sizes(self, cas: "Cascade", V: int, H: int, W: int):
+        """(l2_stride, floats per buffer [feat_l0, feat_l1, feat_l2, tex_0.., exts, ixts]) of a cache for this cascade."""
+        l2s = _i(0)
+        floats = (_ll * SOURCE_CACHE_BUFFERS)()
+        self._check(self.dll.enerf_source_cache_sizes(C.byref(cas), V, H, W, C.byref(l2s), floats), "source_cache_sizes")
+        return l2s.value, list(floats)
+
+    def source_cache_build(self, cache: "SourceCacheStruct", src_inps, exts, ixts, packed, cas: "Cascade", chunk=0, options=None):
+        """FeatureNet + texel packing of ``src_inps`` (V,3,H,W) into the cache's buffers, ``chunk`` (<= 4) images at a time."""
+        nb = self.dll.enerf_source_cache_build_workspace_bytes(cache.H, cache.W)
+        ws = torch.empty(((nb + 3) // 4,), dtype=torch.float32, device=src_inps.device)
+        self._check(self.dll.enerf_source_cache_build(C.byref(cache), _ptr(src_inps), _ptr(exts), _ptr(ixts), _ptr(packed),
+                                                      C.byref(cas), int(chunk), ws.data_ptr(), ws.numel() * 4, _opt(options),
+                                                      self.stream_of(src_inps)), "source_cache_build")
+
+    def forward_cached_workspace_bytes(self, args: "FrameArgs", cache: "SourceCacheStruct") -> int:
+        n = self.dll.enerf_forward_cached_workspace_bytes(C.byref(args), C.byref(cache))
+        if n == 0:
+            raise EnerfError(f"forward_cached: {self.dll.enerf_last_error().decode()}")
+        return n
+
+    def forward_cached(self, args: "FrameArgs", cache: "SourceCacheStruct", view_idx_ptr, stream):
+        """``view_idx_ptr``: address of the (B,S) int32 DEVICE array (never read on the host)."""
+        self._check(self.dll.enerf_forward_cached(C.byref(args), C.byref(cache), view_idx_ptr, stream), "forward_cached")
 
     # -- the steps before / after the path (SURVEY.md 8f rows 3, 4) ---------------------------------
     def gen_rays(self, tar_ext, tar_ixt, Hr, Wr, scale):

@@ -377,8 +377,51 @@ class Network(nn.Module):
         return {k: torch.cat([p[k] for p in parts], dim=1) for k in parts[0]}
 
     def forward(self, batch):
-        """network.py:76-113 / network_human.py:69-119 — one ``enerf_forward`` C call (enerf_amd/csrc/frame.hip)."""
+        """network.py:76-113 / network_human.py:69-119 — one ``enerf_forward`` C call (enerf_amd/csrc/frame.hip).
+        A batch that carries ``source_cache`` (:meth:`cache_sources`) and ``near_views`` (the reference's ``convert_data`` key:
+        the indices of its source views) takes its feature maps from the cache: :meth:`forward_cached`."""
+        if "source_cache" in batch and "near_views" in batch and not self.training:
+            return self.forward_cached(batch["source_cache"], batch["near_views"], batch)
         return self._forward(batch, self.options)
+
+    # -- source-view cache (enerf_amd/source_cache.py) ----------------------------------------------
+    def cache_sources(self, inps, exts, ixts, chunk: int = 0):
+        """FeatureNet maps, render texels and cameras of the V views a scene / time frame draws its source views from
+        (zjumocap/enerf_interactive.py:102-105,138-153), computed once: ``inps`` (V,3,H,W) in [-1,1], ``exts`` (V,4,4),
+        ``ixts`` (V,3,3).  Eval mode and ``feature_backend="hip"`` only."""
+        from .source_cache import SourceCache
+        return SourceCache(self, inps, exts, ixts, chunk)
+
+    def forward_cached(self, cache, view_idx, batch):
+        """``forward`` with the source views named by ``view_idx`` — an int32 DEVICE tensor (B,S) or (S,), e.g. the output of
+        ``EnerfLib.select_views`` — taken from ``cache``; ``batch`` carries ``tar_ext``, ``tar_ixt``, ``near_far`` and optionally
+        ``rays_{i}`` / ``mask_at_box``.  The index is never read on the host.  Bit-identical to ``forward`` on those views.
+        Anything else that holds integer indices — the reference's host-side int64 ``near_views`` (a numpy slice,
+        zjumocap/enerf_interactive.py:208,218), a list, an int64 or host tensor — is converted and uploaded first, which costs a
+        host-to-device copy per frame; only the int32 device tensor is free of it."""
+        if self.training:
+            raise RuntimeError("forward_cached: inference only (call net.eval())")
+        if self.feature_backend != "hip":
+            raise ValueError("forward_cached needs feature_backend='hip'")
+        if cache.packed_gen != self._packed_gen:
+            raise RuntimeError("forward_cached: the network's weights changed (load_state_dict / .to()) after the cache was "
+                               "built; call cache_sources again")
+        if not torch.is_tensor(view_idx):
+            import numpy as np
+            view_idx = torch.from_numpy(np.ascontiguousarray(view_idx))
+        if view_idx.is_floating_point() or view_idx.dtype == torch.bool or view_idx.dim() not in (1, 2):
+            raise ValueError("forward_cached: view_idx must hold integer view indices, (B,S) or (S,)")
+        if view_idx.dtype != torch.int32 or view_idx.device != cache.device or not view_idx.is_contiguous():
+            view_idx = view_idx.to(device=cache.device, dtype=torch.int32).contiguous()
+        B = batch["tar_ext"].shape[0]
+        if view_idx.dim() == 1:
+            if B != 1:
+                raise ValueError(f"forward_cached: view_idx is (S,) but the batch has B={B}; pass (B,S)")
+        elif view_idx.shape[0] != B:
+            raise ValueError(f"forward_cached: view_idx has {view_idx.shape[0]} rows, the batch B={B}")
+        if batch["tar_ext"].device != cache.device:
+            raise ValueError("forward_cached: cache and batch must live on one device")
+        return self._forward(batch, self.options, cache, view_idx)
 
     def _alloc_outputs(self, B, H, W, n_rays, dev):
         """Fresh output tensors of one frame (network.py:93-108 keys) + their addresses per rendered level."""
@@ -406,7 +449,7 @@ class Network(nn.Module):
             self._frames[key] = st
         return st
 
-    def _forward(self, batch, options):
+    def _forward(self, batch, options, cache=None, view_idx=None):
         if self.training:
             # trainer.py:56-63 / losses/enerf.py:16-56: the differentiable path on this network's own parameter modules
             # (BatchNorm batch statistics, autograd, DDP-ready) — enerf_amd/train_path.py
@@ -416,8 +459,12 @@ class Network(nn.Module):
         cas, lib = self.cfg.cas, self.lib
         if self._tex_cache is not None:
             self._tex_cache = None                     # (nn.Module.__setattr__ costs 6 us: only when there is something to drop)
-        src = batch["src_inps"]
-        B, S, _, H, W = src.shape
+        if cache is None:
+            src = batch["src_inps"]
+            B, S, _, H, W = src.shape
+        else:                                          # forward_cached: no images in the batch, the cache has their maps
+            src = batch["tar_ext"]
+            B, S, H, W = src.shape[0], view_idx.shape[-1], cache.H, cache.W
         dev = src.device
         # Host time before the C call is GPU idle time under the reference's sync-per-frame protocol (run.py:62-76: measured
         # 30 us of a 0.80 ms dtu frame), so the per-frame Python work is kept minimal: one stream lookup; everything that depends
@@ -426,7 +473,7 @@ class Network(nn.Module):
         # outputs' addresses are stored, and the OUTPUT tensors of this frame were allocated right after the previous frame's
         # launch (below) — every frame still returns fresh, never-aliased tensors.
         sid = torch.cuda.current_stream(dev).cuda_stream if src.is_cuda else 0
-        st = self._frame_state(sid)
+        st = self._frame_state(sid if cache is None else (sid, "cached"))
         a = st["args"]
         keep = []                                             # tensors whose addresses the call uses
 
@@ -439,10 +486,13 @@ class Network(nn.Module):
             return t.data_ptr()
 
         with torch.no_grad():
-            a.src_inps, a.src_exts, a.src_ixts = ptr(src), ptr(batch["src_exts"]), ptr(batch["src_ixts"])
+            if cache is None:
+                a.src_inps, a.src_exts, a.src_ixts = ptr(src), ptr(batch["src_exts"]), ptr(batch["src_ixts"])
+            else:
+                keep.append(view_idx)
             a.tar_ext, a.tar_ixt, a.near_far = ptr(batch["tar_ext"]), ptr(batch["tar_ixt"]), ptr(batch["near_far"])
             masked = self.human and "mask_at_box" in batch
-            hip_feats = self.feature_backend == "hip"
+            hip_feats = cache is not None or self.feature_backend == "hip"
             rays_of = [batch.get(f"rays_{i}") if cas.render_if[i] else None for i in range(cas.num)]
             sig = (B, S, H, W, hip_feats, masked) + tuple(
                 -1 if not cas.render_if[i] else (-2 if rays_of[i] is None else rays_of[i].shape[1]) for i in range(cas.num))
@@ -454,12 +504,12 @@ class Network(nn.Module):
                 a.B, a.S, a.H, a.W = B, S, H, W
                 pk = st.get("packed")
                 if pk is None or pk[0] != self._packed_gen:   # first frame on this stream / weights changed: (re)pack, wait
-                    names = (["feature_net"] if hip_feats else []) + \
+                    names = (["feature_net"] if hip_feats and cache is None else []) + \
                             [f"cost_reg_{i}" for i in range(cas.num)] + [f"nerf_{i}" for i in range(cas.num) if cas.render_if[i]]
                     pk = (self._packed_gen, {n: self._packed_weights(n).data_ptr() for n in names})
                     st["packed"] = pk
                 pp = pk[1]
-                a.feature_net_packed = pp["feature_net"] if hip_feats else None
+                a.feature_net_packed = pp["feature_net"] if hip_feats and cache is None else None
                 if hip_feats:
                     for l in range(3):
                         a.feats_nchw[l] = None
@@ -526,12 +576,16 @@ class Network(nn.Module):
             if st.get("plan"):                                   # after a static refresh: (re)plan the workspace for these shapes
                 if st["sig"] != (sig, okey):                          # some options change the plan's workspace needs
                     a.workspace, a.workspace_bytes = None, 0
-                    st["need"], st["sig"] = lib.forward_workspace_bytes(a), (sig, okey)
+                    need = lib.forward_workspace_bytes(a) if cache is None else lib.forward_cached_workspace_bytes(a, cache.struct)
+                    st["need"], st["sig"] = need, (sig, okey)
                 if st["ws"] is None or st["ws"].numel() * 4 < st["need"] or st["ws"].device != dev:
                     st["ws"] = torch.empty(((st["need"] + 3) // 4,), dtype=torch.float32, device=dev)
                 a.workspace, a.workspace_bytes = st["ws"].data_ptr(), st["ws"].numel() * 4
                 st["plan"] = False
-            lib.forward(a, sid if src.is_cuda else None)
+            if cache is None:
+                lib.forward(a, sid if src.is_cuda else None)
+            else:
+                lib.forward_cached(a, cache.struct, view_idx.data_ptr(), sid if src.is_cuda else None)
             # the NEXT frame's outputs, allocated while the GPU works on this one
             if not (src.is_cuda and torch.cuda.is_current_stream_capturing()):   # (a capture keeps its allocations private)
                 st["next_out"] = ((sig, dev),) + self._alloc_outputs(B, H, W, n_rays, dev)

@@ -646,6 +646,49 @@ int enerf_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask
                     int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
                     enerf_stream_t stream);
 
+/* ---- source-view cache (ABI v11 grew by these five entries; new symbols only, the version number is unchanged) ----
+ * A static scene (dtu / llff / nerf test splits) or one time frame of the interactive viewer draws the S source views of every
+ * frame from one fixed set of V images: zjumocap/enerf_interactive.py:102-105,138-153 (cache_data) preloads the V views once and
+ * :205-217 only selects and gathers per target camera.  What enerf_forward derives from a source image ALONE — the FeatureNet's
+ * three maps (network.py:58-67,80) and the render texels (network.py:28-34) — is computed once per set here and gathered per
+ * frame by a device-resident view index; the maps of an image do not depend on the other images of the call, so the cached frame
+ * is bit-identical to enerf_forward on the same views gathered by hand.
+ *   enerf_source_cache_t   caller-owned device buffers: the channels-last maps of V views exactly as enerf_feature_net writes them,
+ *       feat_l0 (V,H/4,W/4,32), feat_l1 (V,H/2,W/2,16), feat_l2 (V,H,W,l2_stride); tex[i] (V,Hr_i,Wr_i,TEX_i), the
+ *       enerf_pack_texels_cl image of every rendered level i whose texels the level-2 map does not serve (NULL otherwise);
+ *       exts (V,4,4), ixts (V,3,3).  Every buffer 16-byte aligned.  l2_stride (12: level_2 as render texels, 8: plain) and the
+ *       packed levels follow enerf_forward's rule for the cascade: a cache is valid for the cascade it was sized and built for.
+ *   enerf_source_cache_sizes   floats per buffer for a cascade: floats[0..2] = feat_l0..2, floats[3 + i] = tex[i] (0 = not needed),
+ *       floats[6] = exts, floats[7] = ixts; *l2_stride as above.
+ *   enerf_source_cache_build   src_inps (V,3,H,W) in [-1,1], exts (V,4,4), ixts (V,3,3): runs enerf_feature_net and
+ *       enerf_pack_texels_cl over the views in chunks of `chunk` images (1..4; 0 = 4), so the scratch is
+ *       enerf_source_cache_build_workspace_bytes(H, W) = the FeatureNet workspace of 4 images whatever V is; copies the cameras.
+ *   enerf_forward_cached   Network.forward (network.py:76-113 / network_human.py:69-119) with the feature maps taken from the
+ *       cache: view_idx (B,S) int32 in DEVICE memory (e.g. enerf_select_views' output, :207-210) names the source views of every
+ *       batch element; it is read on the device only, so select -> forward -> pack has no readback and can be captured in a graph.
+ *       Same cascade, outputs and options as enerf_forward; args->src_inps, src_exts, src_ixts, feature_net_packed and feats_nchw
+ *       are ignored; args->S is the number of views per element.  One gather kernel (two launches: the level-2 / texel share on the
+ *       side lane unless options->single_stream) copies the selected views' blocks and camera rows into the frame's workspace;
+ *       from the first warp on the frame is enerf_forward's.  An index outside [0,V) is never dereferenced: that view's maps
+ *       and cameras are filled with NaN, so the frame's output is NaN.  Host-visible mismatches (cache and frame disagree on H, W or
+ *       l2_stride; a texel image missing for a rendered level; V < 1; view_idx NULL) are ENERF_EINVAL, nothing is launched.
+ *       workspace: enerf_forward_cached_workspace_bytes (0 + enerf_last_error() on invalid arguments). */
+typedef struct {
+    float *feat_l0, *feat_l1, *feat_l2;
+    float* tex[ENERF_MAX_LEVELS];
+    float *exts, *ixts;
+    int V, H, W, l2_stride;
+} enerf_source_cache_t;
+#define ENERF_SOURCE_CACHE_BUFFERS (5 + ENERF_MAX_LEVELS)
+int enerf_source_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, int* l2_stride, long long* floats);
+size_t enerf_source_cache_build_workspace_bytes(int H, int W);
+int enerf_source_cache_build(const enerf_source_cache_t* cache, const float* src_inps, const float* exts, const float* ixts,
+                             const float* feature_net_packed, const enerf_cascade_t* cas, int chunk, void* workspace,
+                             size_t workspace_bytes, const enerf_options_t* options, enerf_stream_t stream);
+size_t enerf_forward_cached_workspace_bytes(const enerf_frame_args_t* args, const enerf_source_cache_t* cache);
+int enerf_forward_cached(const enerf_frame_args_t* args, const enerf_source_cache_t* cache, const int* view_idx,
+                         enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
