@@ -30,6 +30,16 @@ void zero_async2(void* p, size_t bytes_p, void* q, size_t bytes_q, hipStream_t s
 static int g_emu_cu_count = 256;
 }  // namespace enerf
 extern "C" void emu_set_cu_count(int n) { enerf::g_emu_cu_count = n > 0 ? n : 256; }
+// the calling thread's launch trace (tests/emu/hip_emu.h; tests/emu_lib.py emu_trace): clear it and switch it on or off; copy it
+// out (returns its length: a caller with a smaller buffer asks again)
+#ifdef ENERF_EMU_TRACE
+extern "C" void emu_trace_reset(int on) { emu::trace().on = on != 0; emu::trace().text.clear(); }
+extern "C" long long emu_trace_read(char* buf, long long cap) {
+    const std::string& t = emu::trace().text;
+    if (buf != nullptr && cap > 0) memcpy(buf, t.data(), t.size() < (size_t)cap ? t.size() : (size_t)cap);
+    return (long long)t.size();
+}
+#endif
 namespace enerf {
 #endif
 int device_cu_count() {

@@ -1,13 +1,14 @@
-// frame.hip — the whole-frame driver enerf_forward (Network.forward, network.py:76-113 / network_human.py:69-119) and
-// the device-side mask_at_box compaction (network_human.py:90-93).  The cascade loop the reference runs in Python is a
-// plan (buffer carving) + ~25 kernel enqueues here, in one C call, on one stream, with no host synchronisation.
+// frame.hip — the whole-frame driver behind enerf_forward / enerf_forward_cached (Network.forward, network.py:76-113 /
+// network_human.py:69-119), the device-side mask_at_box compaction (network_human.py:90-93) and the source-view cache.  The cascade
+// loop the reference runs in Python is a plan (buffer carving) + ~30 kernel enqueues here, in one C call, with no host
+// synchronisation: on the caller's stream, with the leaves of the frame forked onto a side lane (side_lane.h) and joined again.
+// Layout: kernels of this file; FeatDims / make_plan (shapes, workspace); FrameRun (one member function per stage) and
+// run_frame (their sequence); the C entries.
 #include <string.h>
-
-#include <map>
-#include <mutex>
 
 #include "kernels.h"
 #include "prep_job.h"
+#include "side_lane.h"
 
 using namespace enerf;
 
@@ -153,21 +154,13 @@ void launch_gather_sources(const GatherJob& J, int n_img, hipStream_t st) {
 // Frame plan: shapes of every level and the carving of the caller's workspace.
 // =====================================================================================================================
 namespace {
-struct LevelPlan {
-    int D, h, w, C, Hs, Ws;            // volume extent; cost-volume feature channels and source-map size
-    int Hr, Wr, render, masked, F, Ns; // render extent, flags, nerf feature width (C_f + 3), samples per ray
-    long long n_rays;
-    // workspace offsets (floats)
-    size_t proj, dv, nf, vol, feat3d, prob, depth, std, dmvs, tex, rays;
+// the FeatureNet's pyramid (feature_net.py:27-36): level_0 at a quarter of the image with 32 channels .. level_2 at full size with 8
+struct FeatDims {
+    int h[3], w[3], c[3];
+    FeatDims(int H, int W) : h{H / 4, H / 2, H}, w{W / 4, W / 2, W}, c{32, 16, 8} {}
+    long long pixels(int l) const { return (long long)h[l] * w[l]; }
 };
-struct FramePlan {
-    int tex2, hip_feats, cached;
-    size_t f[3], featnet_ws, featnet_ws_bytes, costreg_ws, costreg_ws_bytes;
-    size_t cam_exts, cam_ixts;                     // cached frame: the gathered (B,S,4,4) / (B,S,3,3) camera rows
-    size_t ray_index, ray_count, mask_ws;          // float-sized slots
-    LevelPlan L[ENERF_MAX_LEVELS];
-    size_t total_floats;
-};
+inline int tex_stride(int F) { return 4 * ((F + 3) / 4); }              // floats per render texel: F = C_f + 3, padded to quads
 inline int scaled(int n, double s) { return (int)((double)n * s); }      // python: int(H * scale)
 
 // level_2 is only ever the im_feat of a full-resolution render: then the FeatureNet emits it as render texels
@@ -180,6 +173,40 @@ int cascade_tex2(const enerf_cascade_t& c) {
         }
     return uses > 0 && all_full && c.num <= 2;
 }
+inline int l2_stride(int tex2) { return tex2 ? 12 : 8; }                 // floats per pixel of the level-2 map: texels or features
+inline int l2_stride(const enerf_cascade_t& c) { return l2_stride(cascade_tex2(c)); }
+// level i is rendered straight from the level-2 map (emitted as texels): it has no texel image of its own
+inline bool renders_from_l2(const enerf_cascade_t& c, int i, int tex2) {
+    return c.render_if[i] && c.render_im_feat_level[i] == 2 && tex2;
+}
+// render level i reads feature level render_im_feat_level[i]: the channel count must match, and (same_extent: the HIP
+// FeatureNet's maps, which are never resampled) so must the extent
+int check_render_feat(const char* who, const enerf_cascade_t& c, int i, const FeatDims& fd, int Hr, int Wr, bool same_extent) {
+    const int fl = c.render_im_feat_level[i];
+    REQUIRE(fl >= 0 && fl <= 2 && fd.c[fl] == c.nerf_model_feat_ch[i],
+            "%s: render_im_feat_level[%d]=%d does not have nerf_model_feat_ch=%d channels", who, i, fl, c.nerf_model_feat_ch[i]);
+    if (same_extent)
+        REQUIRE(fd.h[fl] == Hr && fd.w[fl] == Wr, "%s: level %d renders at %dx%d but feature level_%d is %dx%d "
+                "(the HIP FeatureNet path needs render_scale == im_ibr_scale)", who, i, Hr, Wr, fl, fd.h[fl], fd.w[fl]);
+    return ENERF_OK;
+}
+
+struct LevelPlan {
+    int D, h, w, C, Hs, Ws;            // volume extent; cost-volume feature channels and source-map size
+    int Hr, Wr, render, masked, F, Ns; // render extent, flags, nerf feature width (C_f + 3), samples per ray
+    int fl, from_l2;                   // rendered levels: the feature level of the texels; the texels ARE the level-2 map
+    long long n_rays;
+    // workspace offsets (floats)
+    size_t proj, dv, nf, vol, feat3d, prob, depth, std, dmvs, tex, rays;
+};
+struct FramePlan {
+    int tex2, hip_feats, cached;
+    size_t f[3], featnet_ws, featnet_ws_bytes, costreg_ws, costreg_ws_bytes;
+    size_t cam_exts, cam_ixts;                     // cached frame: the gathered (B,S,4,4) / (B,S,3,3) camera rows
+    size_t ray_index, ray_count, mask_ws;          // float-sized slots
+    LevelPlan L[ENERF_MAX_LEVELS];
+    size_t total_floats;
+};
 
 // cached: the frame's feature maps, texels and source cameras come from a source cache (enerf_forward_cached): no FeatureNet
 // scratch, camera slots instead; every other offset rule is enerf_forward's
@@ -203,8 +230,8 @@ int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
     size_t off = 0;
     auto take = [&](size_t nfloats) { size_t r = off; off += (nfloats + 63) / 64 * 64; return r; };   // 256-B aligned
     const long long n_img = (long long)a->B * a->S;
-    const int fh[3] = {a->H / 4, a->H / 2, a->H}, fw[3] = {a->W / 4, a->W / 2, a->W}, fc[3] = {32, 16, 8};
-    for (int l = 0; l < 3; ++l) P->f[l] = take((size_t)n_img * fh[l] * fw[l] * (l == 2 && P->tex2 ? 12 : fc[l]));
+    const FeatDims fd(a->H, a->W);
+    for (int l = 0; l < 3; ++l) P->f[l] = take((size_t)n_img * fd.pixels(l) * (l == 2 ? l2_stride(P->tex2) : fd.c[l]));
     P->featnet_ws_bytes = P->hip_feats && !cached ? enerf_feature_net_workspace_bytes((int)n_img, a->H, a->W) : 0;
     P->featnet_ws = take(P->featnet_ws_bytes / sizeof(float));
     P->cam_exts = P->cam_ixts = 0;
@@ -217,7 +244,7 @@ int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
         L.h = scaled(a->H, c.volume_scale[i]);
         L.w = scaled(a->W, c.volume_scale[i]);
         REQUIRE(i < 3, "forward: level %d has no feature map (FeatureNet has three scales)", i);
-        L.C = fc[i]; L.Hs = fh[i]; L.Ws = fw[i];
+        L.C = fd.c[i]; L.Hs = fd.h[i]; L.Ws = fd.w[i];
         REQUIRE(!(i == 2 && P->tex2), "forward: level_2 texels cannot feed a cost volume");
         REQUIRE(L.D > 0 && L.h > 0 && L.w > 0, "forward: level %d volume is empty", i);
         if (i > 0) REQUIRE(c.depth_inv[i - 1], "forward: cascade levels after a depth-space level are undefined in the "
@@ -244,18 +271,16 @@ int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
         REQUIRE(L.Hr > 1 && L.Wr > 1, "forward: level %d render extent too small", i);
         REQUIRE(a->nerf_packed[i], "forward: nerf_packed[%d] missing", i);
         REQUIRE(a->rgb[i] && a->depth[i] && a->weights[i] && a->depth_mvs[i] && a->std[i], "forward: level %d output missing", i);
-        const int fl = c.render_im_feat_level[i];
-        REQUIRE(fl >= 0 && fl <= 2 && fc[fl] == c.nerf_model_feat_ch[i],
-                "forward: render_im_feat_level[%d]=%d does not have nerf_model_feat_ch=%d channels", i, fl, c.nerf_model_feat_ch[i]);
-        if (P->hip_feats)
-            REQUIRE(fh[fl] == L.Hr && fw[fl] == L.Wr, "forward: level %d renders at %dx%d but feature level_%d is %dx%d "
-                    "(the HIP FeatureNet path needs render_scale == im_ibr_scale)", i, L.Hr, L.Wr, fl, fh[fl], fw[fl]);
-        else {
+        const int rc = check_render_feat("forward", c, i, fd, L.Hr, L.Wr, P->hip_feats);
+        if (rc != ENERF_OK) return rc;
+        L.fl = c.render_im_feat_level[i];
+        L.from_l2 = renders_from_l2(c, i, P->tex2);
+        if (!P->hip_feats) {
             const double up = c.render_scale[i] / c.im_ibr_scale[i];
-            REQUIRE(scaled(fh[fl], up) == L.Hr && scaled(fw[fl], up) == L.Wr,
+            REQUIRE(scaled(fd.h[L.fl], up) == L.Hr && scaled(fd.w[L.fl], up) == L.Wr,
                     "forward: im_feat resolution inconsistent with render_scale / im_ibr_scale at level %d", i);
         }
-        if (!(fl == 2 && P->tex2)) L.tex = take((size_t)n_img * L.Hr * L.Wr * 4 * ((L.F + 3) / 4));
+        if (!L.from_l2) L.tex = take((size_t)n_img * L.Hr * L.Wr * tex_stride(L.F));
         if (a->rays[i] != nullptr) {
             REQUIRE(a->n_rays[i] >= 0, "forward: n_rays[%d] negative", i);
             L.n_rays = a->n_rays[i];
@@ -280,53 +305,433 @@ int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
     P->total_floats = off;
     return ENERF_OK;
 }
-}  // namespace
-}  // namespace enerf
+
+// what the host can see of a cache against the frame / cascade it is used with (enerf_forward_cached, enerf_source_cache_build)
+int check_cache(const char* what, const enerf_source_cache_t* k, const enerf_cascade_t& c, int H, int W) {
+    REQUIRE(k, "%s: null cache", what);
+    REQUIRE(k->V >= 1, "%s: cache has V=%d views", what, k->V);
+    REQUIRE(k->H == H && k->W == W, "%s: cache was built for %dx%d images, the frame has %dx%d", what, k->H, k->W, H, W);
+    const int tex2 = cascade_tex2(c);
+    REQUIRE(k->l2_stride == l2_stride(tex2), "%s: cache has l2_stride=%d, this cascade needs %d (a cache is valid for the cascade it was built for)",
+            what, k->l2_stride, l2_stride(tex2));
+    REQUIRE(k->feat_l0 && k->feat_l1 && k->feat_l2 && k->exts && k->ixts, "%s: null cache buffer", what);
+    size_t bits = (size_t)k->feat_l0 | (size_t)k->feat_l1 | (size_t)k->feat_l2 | (size_t)k->exts | (size_t)k->ixts;
+    for (int i = 0; i < c.num && i < ENERF_MAX_LEVELS; ++i) {
+        if (!c.render_if[i] || renders_from_l2(c, i, tex2)) continue;
+        REQUIRE(k->tex[i], "%s: cache has no texel image for rendered level %d", what, i);
+        bits |= (size_t)k->tex[i];
+    }
+    REQUIRE((bits & 15) == 0, "%s: cache buffers must be 16-byte aligned", what);
+    return ENERF_OK;
+}
 
 // =====================================================================================================================
-// Side lane of a frame.  Level 0 (warp + CostRegNet + depth regression) consumes only the FeatureNet's coarsest map, and
-// its deep small layers leave most of the chip idle (mfma busy 0.05-0.13 on 80-640 tiles); the FeatureNet's top-down half
-// — up2+lat1, smooth1 (level 1's source maps) and the fused up2+lat0+smooth0 (the render texels, the second largest
-// kernel of the frame) — is needed later.  So enerf_forward forks that half onto a library-owned stream right after the
-// trunk and joins it with events before its first consumer: the two chains overlap inside ONE frame.
-// The render of a non-final cascade level (render_if True,True: lego, training-style eval) is a leaf as well — nothing in the
-// next level reads its rgb/depth/weights — so it is forked onto the lane's second stream after the level's depth regression
-// and joined at the end of the frame.
-// One lane (two streams + events) per caller stream, created on first use, never destroyed (process lifetime).
+// The frame driver behind enerf_forward (cache == nullptr) and enerf_forward_cached: one FrameRun on the stack per call, one
+// member function per stage, run_frame (below) is their sequence.  Stages enqueue on the caller's stream `st` unless they say
+// otherwise; the fork/join vocabulary is side_lane.h's record / wait, and need_level(l) is the join in front of the first
+// consumer of feature level l on the caller's stream.  Every stage returns ENERF_OK or an error code; after an error run_frame
+// leaves through bail(), which joins whatever was forked.
 // =====================================================================================================================
+// A forked render is a leaf that shares the device with the next level.  As one persistent block per compute unit (130 KB of
+// LDS each at C = 32) it kept the next level's LDS-staged kernels off every CU until its blocks exited; on HALF of the CUs,
+// with the balanced tile deal, the next level starts at once and the leaf ends under its small layers: lego 543 -> 558
+// frames/s (64 blocks 509, 96: 556, 128: 558, 160: 546, all 256: 535; profiles/r06_ab_bg_render_blocks.txt)
+constexpr int kBgRenderDiv = 2;          // a forked render's persistent blocks = compute units / this
+
+struct FrameRun {
+    const enerf_frame_args_t* a = nullptr;
+    const enerf_source_cache_t* cache = nullptr;     // cached frame: the maps, texels and cameras come from here
+    const int* view_idx = nullptr;
+    FramePlan P;
+    hipStream_t st = nullptr;            // the caller's stream
+    hipStream_t cur = nullptr;           // the stream the current stage is enqueued on (the lane's for a forked render)
+    float* ws = nullptr;
+    int n_img = 0;
+    float* f[3] = {nullptr, nullptr, nullptr};       // the feature maps, channels-last
+    const float *src_exts = nullptr, *src_ixts = nullptr;   // the batch's, or (cached frame) the rows the gather leaves in the workspace
+    int *ray_index = nullptr, *ray_count = nullptr;
+    // ---- side lane ----
+    SideLane* lane = nullptr;
+    std::unique_lock<std::mutex> lane_busy;          // held until this call has enqueued its last join (side_lane.h)
+    bool forked = false;                 // the sources' later half runs on the side stream
+    int joined[3] = {1, 1, 1};           // feature level l is visible to the caller's stream
+    int gate_mode = 1;                   // see enerf_options_t.side_gate (resolved by featnet_gate)
+    bool stage2_enqueued = true;         // the FeatureNet's last stage (smooth0) has been enqueued (false while gated)
+    int stage2_rc = ENERF_OK;
+    int render_forks = 0;                // renders of non-final levels enqueued on the lane's render stream
+    // ---- the camera-only preparation riding in the frame's first launch (prep_job.h) ----
+    PrepJob job;
+    int prep_carried = 0;                // a kernel took the job (the fused conv0 pair); otherwise the level loop launches the prep kernels
+    // ---- hand-off from level i - 1 to level i ----
+    const float *pdepth = nullptr, *pstd = nullptr, *pnf = nullptr;
+    int hp = 0, wp = 0;
+    const float *pending_prob = nullptr, *pending_dv = nullptr;    // a depth regression deferred into the next level's prep
+    int pending_D = 0, pending_inv = 0;
+    // ---- inside level i ----
+    int vol_planar = 0;                  // the volume goes to conv0 as channel-quad planes
+    hipStream_t rs = nullptr;            // the stream of the level's texel / ray / render stages
+    bool render_forked = false;
+    const float *tex = nullptr, *rays8 = nullptr;
+
+    const enerf_cascade_t& cas() const { return a->cas; }
+    bool single_stream() const { return a->options && a->options->single_stream; }
+    float* std_of(int i) const { return P.L[i].render ? a->std[i] : ws + P.L[i].std; }
+
+    void mark(int slot) {
 #ifndef ENERF_EMU
-namespace {
-struct SideLane { hipStream_t stream, rstream; hipEvent_t trunk, l1, l2, fork, done; std::mutex busy; };
-SideLane* side_lane(hipStream_t main) {
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, SideLane*> lanes;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    auto key = std::make_pair(dev, main);
-    auto it = lanes.find(key);
-    if (it != lanes.end()) return it->second;
-    SideLane* L = new SideLane();
-    // lowest priority: the lanes carry leaves of the frame, the caller's stream carries its critical path — when both have
-    // workgroups waiting, the chain everything else depends on should get the compute units first (a GPU-filling smooth0
-    // on the lane stretched a small level-0 layer on the caller's stream 10x at 1024x1024: zju 430 -> 437 frames/s)
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    // (a CU-masked lane stream — hipExtStreamCreateWithCUMask keeping 4 / 6 / 7 of every 8 CUs, so that the chain's small layers always
-    // find free CUs — measured round 6: dtu 1320 -> 962 frames/s, zju 555 -> 479 whatever the mask: profiles/r06_ab_lane_cu_mask.txt)
-    bool ok = hipStreamCreateWithPriority(&L->stream, hipStreamNonBlocking, least) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&L->trunk, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&L->l1, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&L->l2, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamCreateWithPriority(&L->rstream, hipStreamNonBlocking, least) == hipSuccess;   // renders of non-final levels
-    ok = ok && hipEventCreateWithFlags(&L->fork, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&L->done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { delete L; L = nullptr; (void)hipGetLastError(); }
-    lanes[key] = L;                                  // a failed creation is remembered: the frame then runs on one stream
-    return L;
+        if (a->stage_events != nullptr && a->stage_events[slot] != nullptr) hipEventRecord((hipEvent_t)a->stage_events[slot], cur);
+#else
+        (void)slot;
+#endif
+    }
+    bool take_lane() {                   // this caller stream's lane, locked for the rest of the call; false = one stream
+        if (!single_stream()) lane = side_lane(st);
+        if (lane != nullptr) lane_busy = std::unique_lock<std::mutex>(lane->busy);
+        return lane != nullptr;
+    }
+    void need_level(int l) {             // call before the first consumer of f[l] on the caller's stream
+        if (forked && !joined[l]) { lane->wait(kLaneMain, l == 1 ? kEvL1 : kEvL2); joined[l] = 1; }
+    }
+    int bail(int code) {                 // error exit: never leave a lane stream un-joined
+        if (render_forks > 0) { lane->record(kEvDone, kLaneRender); lane->wait(kLaneMain, kEvDone); }
+        need_level(1); need_level(2);
+        return code;
+    }
+    int finish() {
+        if (render_forks > 0) lane->wait(kLaneMain, kEvDone);        // join the forked renders
+        need_level(1); need_level(2);    // the caller's stream never returns ahead of the side lane
+        return check_launch("forward");
+    }
+
+    // the plan, and everything the host can refuse before the first launch
+    int begin(const enerf_frame_args_t* args, const enerf_source_cache_t* k, const int* idx, enerf_stream_t stream) {
+        a = args; cache = k; view_idx = idx;
+        int rc = make_plan(a, &P, cache != nullptr);
+        if (rc != ENERF_OK) return rc;
+        if (cache != nullptr) {
+            rc = check_cache("forward_cached", cache, a->cas, a->H, a->W);
+            if (rc != ENERF_OK) return rc;
+            REQUIRE(view_idx, "forward_cached: null view_idx (a (B,S) int32 device array)");
+        }
+        REQUIRE(a->workspace, "forward: null workspace");
+        if (a->workspace_bytes < P.total_floats * sizeof(float))
+            return fail(ENERF_EWORKSPACE, "forward: workspace too small (%zu < %zu bytes)", a->workspace_bytes,
+                        P.total_floats * sizeof(float));
+        st = cur = rs = (hipStream_t)stream;
+        ws = (float*)a->workspace;
+        n_img = a->B * a->S;
+        for (int l = 0; l < 3; ++l) f[l] = ws + P.f[l];
+        src_exts = cache ? ws + P.cam_exts : a->src_exts;
+        src_ixts = cache ? ws + P.cam_ixts : a->src_ixts;
+        return ENERF_OK;
+    }
+
+    // a caller-independent early start for the mask compaction: it only depends on the batch
+    void start_mask_compaction() {
+        const LevelPlan& last = P.L[cas().num - 1];
+        ray_index = a->ray_index; ray_count = a->ray_count;
+        if (!(last.render && last.masked)) return;
+        if (!ray_index) { ray_index = (int*)(ws + P.ray_index); ray_count = (int*)(ws + P.ray_count); }
+        if (!a->ray_index_ready)
+            launch_mask_compact(a->mask_at_box, a->mask_elem_bytes, last.n_rays, ray_index, ray_count, ws + P.mask_ws, st);
+    }
+
+    // The camera-only preparation — level 0's depth planes and EVERY level's projection matrices (utils.py:35-55, 98-111) — rides
+    // in the frame's first launch (prep_job.h): its blocks run beside conv0's instead of as a launch of their own between the trunk
+    // and the warp.  Only the HIP FeatureNet has that launch: the NCHW and cached frames keep the level loop's own prep launches (a
+    // cached frame's preparation reads the GATHERED camera rows).
+    void make_prep_job() {
+        memset(&job, 0, sizeof(job));
+        if (!P.hip_feats || cache != nullptr) return;
+        const enerf_cascade_t& c = cas();
+        const LevelPlan& L0 = P.L[0];
+        job.near_far = a->near_far; job.dv = ws + L0.dv; job.nf = ws + L0.nf;
+        job.B = a->B; job.D = L0.D; job.h = L0.h; job.w = L0.w; job.depth_inv = c.depth_inv[0];
+        for (int i = 0; i < c.num && i < 3; ++i)
+            job.pj[i] = ProjJob{a->src_ixts, a->src_exts, a->tar_ixt, a->tar_ext, ws + P.L[i].proj, a->S, (float)c.im_feat_scale[i],
+                                (float)c.volume_scale[i]};
+        job.nblocks = prep_job_blocks(a->B, L0.D, L0.h, L0.w, 256);
+    }
+
+    // ---- sources, cached frame: gather the selected views' maps, texels and cameras instead of computing them.  Level 0 / level 1
+    // maps, the non-final levels' texels and the cameras (everything the chain needs first) on the caller's stream; the level-2 map
+    // and the last level's texels, two thirds of the bytes and needed only by the final render, on the side stream.
+    int sources_cached() {
+        const enerf_cascade_t& c = cas();
+        const FeatDims fd(a->H, a->W);
+        GatherJob main_job, side_job;
+        memset(&main_job, 0, sizeof(main_job));
+        memset(&side_job, 0, sizeof(side_job));
+        main_job.V = side_job.V = cache->V;
+        main_job.view_idx = side_job.view_idx = view_idx;
+        main_job.exts = cache->exts; main_job.ixts = cache->ixts;
+        main_job.dst_exts = ws + P.cam_exts; main_job.dst_ixts = ws + P.cam_ixts;
+        auto add = [](GatherJob& J, const float* src, float* dst, long long floats_per_view) {
+            J.seg[J.nseg++] = GatherSeg{reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), floats_per_view / 4};
+        };
+        add(main_job, cache->feat_l0, f[0], fd.pixels(0) * fd.c[0]);
+        add(main_job, cache->feat_l1, f[1], fd.pixels(1) * fd.c[1]);
+        bool uses2 = c.num >= 3;                      // level_2 feeds a third level's cost volume, or IS a render's texels (stride 12);
+        for (int i = 0; i < c.num; ++i)               // a render from the plain map reads its own texel image instead
+            uses2 = uses2 || P.L[i].from_l2;
+        if (uses2) add(side_job, cache->feat_l2, f[2], fd.pixels(2) * cache->l2_stride);
+        for (int i = 0; i < c.num; ++i) {
+            const LevelPlan& L = P.L[i];
+            if (!L.render || L.from_l2) continue;
+            add(i + 1 < c.num ? main_job : side_job, cache->tex[i], ws + L.tex, (long long)L.Hr * L.Wr * tex_stride(L.F));
+        }
+        if (side_job.nseg > 0 && take_lane()) {
+            lane->record(kEvTrunk, kLaneMain);         // the lane starts behind the previous frame and the producer of view_idx
+            lane->wait(kLaneSide, kEvTrunk);
+            launch_gather_sources(main_job, n_img, st);
+            launch_gather_sources(side_job, n_img, lane->stream[kLaneSide]);
+            lane->record(kEvL1, kLaneSide);
+            lane->record(kEvL2, kLaneSide);
+            forked = true; joined[1] = 1; joined[2] = 0;       // (level 1 came with the caller's stream)
+        } else {
+            for (int s = 0; s < side_job.nseg; ++s) main_job.seg[main_job.nseg++] = side_job.seg[s];
+            launch_gather_sources(main_job, n_img, st);
+        }
+        return check_launch("forward_cached: gather");
+    }
+
+    // ---- sources, HIP FeatureNet (feature_net.py:27-36) -> channels-last maps; level_2 straight to render texels when it can.
+    // With a lane: the trunk on the caller's stream, the top-down half forked behind it.
+    int featnet_stage(int stage, hipStream_t s) {
+        const bool first = stage == ENERF_FEAT_ALL || stage == ENERF_FEAT_TRUNK;
+        return feature_net_stage_job(a->feature_net_packed, a->src_inps, n_img, a->H, a->W, f[0], f[1], f[2], l2_stride(P.tex2),
+                                     ws + P.featnet_ws, P.featnet_ws_bytes, stage, a->options, s,
+                                     first && job.nblocks > 0 ? &job : nullptr, first ? &prep_carried : nullptr);
+    }
+    // The last stage (lat0 + smooth0 -> render texels) is needed only by the final render.  Enqueued with the fork (default) it
+    // shares the chip with level 0; GATED (enerf_options_t.side_gate >= 2) it is enqueued later, from inside the last level's cost
+    // regularisation, behind an event, to run beside that level's small deep layers instead.  Measured in round 3
+    // (profiles/r03_ab_side_gate.txt): gating LOSES 1-2 % on all three workloads — the early start wins.
+    void featnet_gate() {
+        const enerf_cascade_t& c = cas();
+        gate_mode = a->options ? a->options->side_gate : 0;
+        if (gate_mode == 0) gate_mode = 1;
+        const int lastl = c.num - 1;
+        const bool gateable = c.num >= 2 && P.tex2 && c.render_if[lastl] && c.render_im_feat_level[lastl] == 2;
+        for (int l = 0; l < lastl && gateable; ++l)                       // nobody before the last level may need level_2
+            if (c.render_if[l] && c.render_im_feat_level[l] == 2) gate_mode = 1;
+        if (!gateable) gate_mode = 1;
+    }
+    int sources_featnet() {
+        if (!take_lane()) return featnet_stage(ENERF_FEAT_ALL, st);
+        int rc = featnet_stage(ENERF_FEAT_TRUNK, st);
+        if (rc != ENERF_OK) return rc;
+        lane->record(kEvTrunk, kLaneMain);
+        lane->wait(kLaneSide, kEvTrunk);
+        rc = featnet_stage(ENERF_FEAT_LEVEL1, lane->stream[kLaneSide]);
+        lane->record(kEvL1, kLaneSide);
+        featnet_gate();
+        if (gate_mode == 1) {
+            if (rc == ENERF_OK) rc = featnet_stage(ENERF_FEAT_LEVEL2, lane->stream[kLaneSide]);
+            lane->record(kEvL2, kLaneSide);
+        } else
+            stage2_enqueued = false;         // level_cost_reg of the last level enqueues it
+        forked = true; joined[1] = joined[2] = 0;
+        return rc;
+    }
+    // deferred enqueue of the FeatureNet's last stage on the side stream, behind an event recorded on the caller's stream NOW
+    void enqueue_stage2() {
+        if (stage2_enqueued || lane == nullptr) return;
+        lane->record(kEvFork, kLaneMain);                                 // "the chain has reached this point"
+        lane->wait(kLaneSide, kEvFork);
+        stage2_rc = featnet_stage(ENERF_FEAT_LEVEL2, lane->stream[kLaneSide]);
+        lane->record(kEvL2, kLaneSide);
+        stage2_enqueued = true;
+    }
+
+    // ---- sources, NCHW maps from torch: the levels that feed a cost volume (texels are packed from NCHW in level_texels) ----
+    int sources_nchw() {
+        const FeatDims fd(a->H, a->W);
+        for (int l = 0; l < cas().num; ++l) launch_channels_last(a->feats_nchw[l], f[l], n_img, fd.c[l], fd.pixels(l), fd.c[l], st);
+        return ENERF_OK;
+    }
+
+    // ---- level i: projection matrices and depth hypotheses.  The previous level's depth regression rides in this launch when that
+    // level is not rendered (its depth / std are then only this level's inputs): one launch instead of two on the critical chain
+    // between the levels.
+    int level_prep(int i) {
+        const enerf_cascade_t& c = cas();
+        const LevelPlan& L = P.L[i];
+        float *proj = ws + L.proj, *dv = ws + L.dv, *nf = ws + L.nf;
+        bool prep_done = false;
+        if (pending_prob != nullptr) {
+            // (the level's projection matrices are already there when the frame's first launch carried the preparation job)
+            prep_done = launch_regress_and_values(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->S, (float)c.im_feat_scale[i],
+                                                  (float)c.volume_scale[i], prep_carried && i < 3 ? nullptr : proj, pending_prob, pending_dv, pnf, pending_D, hp, wp,
+                                                  pending_inv, const_cast<float*>(pdepth), const_cast<float*>(pstd), a->B, L.D,
+                                                  L.h, L.w, c.depth_inv[i], dv, nf, st);
+            if (!prep_done)         // shape outside the fused kernel's limits: the two separate launches
+                launch_depth_regression(pending_prob, pending_dv, a->B, pending_D, hp, wp, pending_inv,
+                                        const_cast<float*>(pdepth), const_cast<float*>(pstd), nullptr, st);
+            pending_prob = nullptr;
+        }
+        if (i == 0 && prep_carried) prep_done = true;                  // level 0: planes + matrices came with the first launch
+        int rc;
+        if (!prep_done)
+            rc = enerf_level_prep(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->B, a->S, (float)c.im_feat_scale[i],
+                                  (float)c.volume_scale[i], proj, a->near_far, pdepth, pstd, pnf, L.D, L.h, L.w, hp, wp,
+                                  c.depth_inv[i], dv, nf, st);
+        else
+            rc = check_launch("level_prep");
+        if (rc == ENERF_OK) mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_PREP));
+        return rc;
+    }
+
+    // ---- level i: the warped feature volume, as channel-quad planes when conv0 runs on the asynchronously staged kernel ----
+    int level_volume(int i) {
+        const LevelPlan& L = P.L[i];
+        float *proj = ws + L.proj, *dv = ws + L.dv, *vol = ws + L.vol;
+        need_level(i);                                                     // level i's source maps (side stream for i >= 1)
+        vol_planar = cost_reg_wants_planar_volume(resolve_options(a->options), L.C, a->B, L.D, L.h, L.w) ? 1 : 0;
+        int rc;
+        if (!vol_planar)
+            rc = enerf_build_feature_volume(f[i], proj, dv, a->B, a->S, L.C, L.Hs, L.Ws, L.D, L.h, L.w, vol, st);
+        else {      // same argument checks as the C entry (shapes come from the validated plan; the 32-bit limits are re-checked)
+            REQUIRE((long long)a->B * a->S * L.Hs * L.Ws * L.C < (1LL << 32) && (long long)L.Hs * L.Ws < (1LL << 23) &&
+                    (long long)a->B * L.D * L.h * L.w * (L.C / 4) < (1LL << 31) && (long long)L.h * L.w < (1LL << 23) &&
+                    (long long)a->B * L.D <= 65535 && (long long)a->B * L.D * L.h < (1LL << 23) && L.w < (1 << 23),
+                    "forward: level %d volume too large for 32-bit indices / the grid-carried voxel decomposition", i);
+            launch_feature_volume(f[i], proj, dv, a->B, a->S, L.C, L.Hs, L.Ws, L.D, L.h, L.w, vol, st, 1);
+            rc = check_launch("build_feature_volume");
+        }
+        if (rc == ENERF_OK) mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_VOLUME));
+        return rc;
+    }
+
+    // ---- level i: CostRegNet.  On the last level a gated FeatureNet stage 2 is enqueued around it: before it (side_gate 3), from
+    // its hook after conv0 (2) or conv2 (4), and in any case behind it (an error path inside cost_reg skips the hook).
+    int level_cost_reg(int i) {
+        const LevelPlan& L = P.L[i];
+        const CostRegHook hook = {[](void* self) { static_cast<FrameRun*>(self)->enqueue_stage2(); }, this, gate_mode == 4 ? 2 : 0};
+        const CostRegHook* hk = nullptr;
+        const bool gated_here = !stage2_enqueued && i == cas().num - 1;
+        if (gated_here) {
+            if (gate_mode == 3) enqueue_stage2(); else hk = &hook;
+        }
+        int rc = cost_reg_run(a->cost_reg_packed[i], L.C, i != 0, ws + L.vol, vol_planar, a->B, L.D, L.h, L.w, ws + L.feat3d, ws + L.prob,
+                              ws + P.costreg_ws, P.costreg_ws_bytes, a->options, st, hk);
+        if (gated_here) enqueue_stage2();
+        if (rc == ENERF_OK && stage2_rc != ENERF_OK) rc = stage2_rc;
+        if (rc == ENERF_OK) mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_COST_REG));
+        return rc;
+    }
+
+    // ---- level i: depth regression — now, or (level not rendered, a next level follows) deferred into that level's prep launch;
+    // then the hand-off to level i + 1
+    int level_depth(int i) {
+        const enerf_cascade_t& c = cas();
+        const LevelPlan& L = P.L[i];
+        float *prob = ws + L.prob, *dv = ws + L.dv, *depth = ws + L.depth, *std = std_of(i);
+        const bool defer_regression = !L.render && i + 1 < c.num && !(a->options && a->options->fuse_depth_prep == 1);
+        if (defer_regression) { pending_prob = prob; pending_dv = dv; pending_D = L.D; pending_inv = c.depth_inv[i]; }
+        else launch_depth_regression(prob, dv, a->B, L.D, L.h, L.w, c.depth_inv[i], depth, std, L.render ? a->depth_mvs[i] : nullptr, st);
+        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_DEPTH_REG));
+        pdepth = depth; pstd = std; pnf = ws + L.nf; hp = L.h; wp = L.w;
+        return ENERF_OK;
+    }
+
+    // ---- rendered level i, texels: unpreprocess + cat (network.py:28-34) as the channels-last gather source.  The texel source is
+    // joined here; a non-final level's render is a leaf of the frame, so its three stages are forked onto the render stream (its
+    // inputs are complete on the caller's stream here).
+    int level_texels(int i) {
+        const enerf_cascade_t& c = cas();
+        const LevelPlan& L = P.L[i];
+        const FeatDims fd(a->H, a->W);
+        const int fl = L.fl, TEX = tex_stride(L.F);
+        if (cache == nullptr || L.from_l2) need_level(fl);
+        rs = st; render_forked = false;
+        if (forked && i + 1 < c.num && !L.masked) {
+            if (render_forks > 0) lane->wait(kLaneRender, kEvDone);       // (ordering only: same stream anyway)
+            lane->record(kEvFork, kLaneMain);
+            lane->wait(kLaneRender, kEvFork);
+            rs = cur = lane->stream[kLaneRender]; render_forked = true; ++render_forks;
+        }
+        int rc = ENERF_OK;
+        if (L.from_l2) tex = f[2];
+        else if (cache != nullptr) {                                       // gathered with the maps; the last level's on the side stream
+            if (i + 1 == c.num) need_level(2);
+            tex = ws + L.tex;
+        } else {
+            float* t = ws + L.tex;
+            if (P.hip_feats)
+                rc = enerf_pack_texels_cl(f[fl], fd.c[fl], a->src_inps, a->H, a->W, L.Hr, L.Wr, TEX, n_img, t, rs);
+            else
+                rc = enerf_pack_img_feat_rgb(a->feats_nchw[fl], fd.c[fl], fd.h[fl], fd.w[fl], a->src_inps, a->H, a->W, L.Hr, L.Wr,
+                                             TEX, n_img, t, rs);
+            tex = t;
+        }
+        if (rc == ENERF_OK) mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_TEXELS));
+        return rc;
+    }
+
+    // ---- rendered level i, rays: the batch's, or the full image generated here (enerf_utils.py:61-71) ----
+    int level_rays(int i) {
+        const LevelPlan& L = P.L[i];
+        rays8 = a->rays[i];
+        if (rays8 != nullptr) return ENERF_OK;
+        float* r = ws + L.rays;
+        rays8 = r;
+        return enerf_gen_rays(a->tar_ext, a->tar_ixt, a->B, L.Hr, L.Wr, (float)cas().render_scale[i], r, rs);
+    }
+
+    // ---- rendered level i: build_rays + render_rays (utils.py:390-420, network.py:24-43), one launch ----
+    int level_render(int i) {
+        const enerf_cascade_t& c = cas();
+        const LevelPlan& L = P.L[i];
+        enerf_render_args_t ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.tex = tex; ra.vol = ws + L.feat3d; ra.src_exts = src_exts; ra.src_ixts = src_ixts; ra.tar_ext = a->tar_ext;
+        ra.packed = a->nerf_packed[i];
+        ra.rgb = a->rgb[i]; ra.depth = a->depth[i]; ra.weights = a->weights[i];
+        ra.B = a->B; ra.N = (int)L.n_rays; ra.S = a->S; ra.n_samples = L.Ns; ra.depth_inv = c.depth_inv[i];
+        ra.Hr = L.Hr; ra.Wr = L.Wr; ra.F = L.F; ra.D = L.D; ra.h = L.h; ra.w = L.w; ra.white_bkgd = c.white_bkgd;
+        ra.render_scale = (float)c.render_scale[i];
+        ra.rays8 = rays8; ra.depth_map = ws + L.depth; ra.std_map = std_of(i); ra.nf_map = ws + L.nf; ra.map_h = L.h; ra.map_w = L.w;
+        ra.options = a->options;
+        if (render_forked) ra.max_blocks = device_cu_count() / kBgRenderDiv;
+        if (L.masked) {
+            ra.ray_index = ray_index; ra.ray_count = ray_count; ra.scatter_rgb = 1;
+            zero_async(a->rgb[i], (size_t)L.n_rays * 3 * sizeof(float), rs);      // torch.zeros_like(...), network_human.py:103
+        }
+        const int rc = enerf_render_rays(&ra, rs);
+        if (rc != ENERF_OK) return rc;
+        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_RENDER));
+        if (render_forked) { lane->record(kEvDone, kLaneRender); cur = st; }
+        return ENERF_OK;
+    }
+};
+
+int run_frame(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
+    FrameRun R;
+    int rc = R.begin(a, cache, view_idx, stream);
+    if (rc != ENERF_OK) return rc;
+    R.mark(ENERF_STAGE_BEGIN);
+    R.start_mask_compaction();
+    R.make_prep_job();
+    rc = cache != nullptr ? R.sources_cached() : R.P.hip_feats ? R.sources_featnet() : R.sources_nchw();
+    if (rc != ENERF_OK) return R.bail(rc);
+    R.mark(ENERF_STAGE_FEATURE_NET);
+    for (int i = 0; i < a->cas.num; ++i) {
+        rc = R.level_prep(i);
+        if (rc == ENERF_OK) rc = R.level_volume(i);
+        if (rc == ENERF_OK) rc = R.level_cost_reg(i);
+        if (rc == ENERF_OK) rc = R.level_depth(i);
+        if (rc == ENERF_OK && R.P.L[i].render) {
+            rc = R.level_texels(i);
+            if (rc == ENERF_OK) rc = R.level_rays(i);
+            if (rc == ENERF_OK) rc = R.level_render(i);
+        }
+        if (rc != ENERF_OK) return R.bail(rc);
+    }
+    return R.finish();
 }
 }  // namespace
-#endif
+}  // namespace enerf
 
 extern "C" {
 
@@ -347,376 +752,6 @@ size_t enerf_forward_workspace_bytes(const enerf_frame_args_t* a) {
     return P.total_floats * sizeof(float);
 }
 
-}  // extern "C"
-
-namespace {
-// what the host can see of a cache against the frame / cascade it is used with (enerf_forward_cached, enerf_source_cache_build)
-int check_cache(const char* what, const enerf_source_cache_t* k, const enerf_cascade_t& c, int H, int W) {
-    REQUIRE(k, "%s: null cache", what);
-    REQUIRE(k->V >= 1, "%s: cache has V=%d views", what, k->V);
-    REQUIRE(k->H == H && k->W == W, "%s: cache was built for %dx%d images, the frame has %dx%d", what, k->H, k->W, H, W);
-    const int l2s = cascade_tex2(c) ? 12 : 8;
-    REQUIRE(k->l2_stride == l2s, "%s: cache has l2_stride=%d, this cascade needs %d (a cache is valid for the cascade it was built for)",
-            what, k->l2_stride, l2s);
-    REQUIRE(k->feat_l0 && k->feat_l1 && k->feat_l2 && k->exts && k->ixts, "%s: null cache buffer", what);
-    size_t bits = (size_t)k->feat_l0 | (size_t)k->feat_l1 | (size_t)k->feat_l2 | (size_t)k->exts | (size_t)k->ixts;
-    for (int i = 0; i < c.num && i < ENERF_MAX_LEVELS; ++i) {
-        if (!c.render_if[i] || (c.render_im_feat_level[i] == 2 && l2s == 12)) continue;
-        REQUIRE(k->tex[i], "%s: cache has no texel image for rendered level %d", what, i);
-        bits |= (size_t)k->tex[i];
-    }
-    REQUIRE((bits & 15) == 0, "%s: cache buffers must be 16-byte aligned", what);
-    return ENERF_OK;
-}
-
-// The frame driver behind enerf_forward (cache == nullptr) and enerf_forward_cached.
-int run_frame(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
-    FramePlan P;
-    int rc = make_plan(a, &P, cache != nullptr);
-    if (rc != ENERF_OK) return rc;
-    if (cache != nullptr) {
-        rc = check_cache("forward_cached", cache, a->cas, a->H, a->W);
-        if (rc != ENERF_OK) return rc;
-        REQUIRE(view_idx, "forward_cached: null view_idx (a (B,S) int32 device array)");
-    }
-    REQUIRE(a->workspace, "forward: null workspace");
-    if (a->workspace_bytes < P.total_floats * sizeof(float))
-        return fail(ENERF_EWORKSPACE, "forward: workspace too small (%zu < %zu bytes)", a->workspace_bytes,
-                    P.total_floats * sizeof(float));
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = (float*)a->workspace;
-    const enerf_cascade_t& c = a->cas;
-    const int n_img = a->B * a->S;
-    hipStream_t cur = st;                // the stream the current stage is enqueued on (the lane's for a forked render)
-    auto mark = [&](int slot) {
-#ifndef ENERF_EMU
-        if (a->stage_events != nullptr && a->stage_events[slot] != nullptr) hipEventRecord((hipEvent_t)a->stage_events[slot], cur);
-#else
-        (void)slot;
-#endif
-    };
-    mark(ENERF_STAGE_BEGIN);
-    // a caller-independent early start for the mask compaction: it only depends on the batch
-    int *ray_index = a->ray_index, *ray_count = a->ray_count;
-    const LevelPlan& last = P.L[c.num - 1];
-    if (last.render && last.masked) {
-        if (!ray_index) { ray_index = (int*)(ws + P.ray_index); ray_count = (int*)(ws + P.ray_count); }
-        if (!a->ray_index_ready)
-            launch_mask_compact(a->mask_at_box, a->mask_elem_bytes, last.n_rays, ray_index, ray_count, ws + P.mask_ws, st);
-    }
-
-    // the source cameras: the batch's, or (cached frame) the rows the gather leaves in the workspace
-    const float* src_exts = cache ? ws + P.cam_exts : a->src_exts;
-    const float* src_ixts = cache ? ws + P.cam_ixts : a->src_ixts;
-    // ---- FeatureNet (feature_net.py:27-36) -> channels-last maps; level_2 straight to render texels when it can ----
-    float* f[3] = {ws + P.f[0], ws + P.f[1], ws + P.f[2]};
-    const int fh[3] = {a->H / 4, a->H / 2, a->H}, fw[3] = {a->W / 4, a->W / 2, a->W}, fc[3] = {32, 16, 8};
-    bool forked = false;                 // the FeatureNet's top-down half runs on the side lane
-    int gate_mode = 1;                   // see enerf_options_t.side_gate (resolved below)
-    bool stage2_enqueued = true;         // the FeatureNet's last stage (smooth0) has been enqueued (false while gated)
-    int stage2_rc = ENERF_OK;
-    int render_forks = 0;                // renders of non-final levels enqueued on the lane's second stream
-    int joined[3] = {1, 1, 1};           // feature level l is visible to the caller's stream
-#ifndef ENERF_EMU
-    SideLane* lane = nullptr;
-    // the lane's events are shared by every frame enqueued on this caller stream: two host threads calling enerf_forward on
-    // the SAME stream would interleave hipEventRecord / hipStreamWaitEvent pairs (a wait could bind to the other call's
-    // record).  The enqueue is serialised per lane; the lock is held until this call has enqueued its last join.
-    std::unique_lock<std::mutex> lane_busy;
-#endif
-    auto need_level = [&](int l) {       // call before the first consumer of f[l] on the caller's stream
-#ifndef ENERF_EMU
-        if (forked && !joined[l]) { hipStreamWaitEvent(st, l == 1 ? lane->l1 : lane->l2, 0); joined[l] = 1; }
-#else
-        (void)l;
-#endif
-    };
-    auto bail = [&](int code) {          // error exit after a fork: never leave a lane stream un-joined
-#ifndef ENERF_EMU
-        if (render_forks > 0) { hipEventRecord(lane->done, lane->rstream); hipStreamWaitEvent(st, lane->done, 0); }
-#endif
-        need_level(1); need_level(2);
-        return code;
-    };
-    // The camera-only preparation — level 0's depth planes and EVERY level's projection matrices (utils.py:35-55, 98-111) — rides
-    // in the frame's first launch (prep_job.h): its blocks run beside conv0's instead of as a launch of their own between the trunk
-    // and the warp.  prep_carried: a kernel took the job (the fused conv0 pair; otherwise the level loop launches the prep kernels).
-    int prep_carried = 0;
-    PrepJob job;
-    memset(&job, 0, sizeof(job));
-#ifndef ENERF_PREP_JOB
-#define ENERF_PREP_JOB 1             // 0 (A/B): the preparation as launches of its own inside the level loop (rounds 1 - 5)
-#endif
-    if (P.hip_feats && ENERF_PREP_JOB && cache == nullptr) {
-        const LevelPlan& L0 = P.L[0];
-        job.near_far = a->near_far; job.dv = ws + L0.dv; job.nf = ws + L0.nf;
-        job.B = a->B; job.D = L0.D; job.h = L0.h; job.w = L0.w; job.depth_inv = c.depth_inv[0];
-        for (int i = 0; i < c.num && i < 3; ++i)
-            job.pj[i] = ProjJob{a->src_ixts, a->src_exts, a->tar_ixt, a->tar_ext, ws + P.L[i].proj, a->S, (float)c.im_feat_scale[i],
-                                (float)c.volume_scale[i]};
-        job.nblocks = prep_job_blocks(a->B, L0.D, L0.h, L0.w, 256);
-    }
-    if (cache != nullptr) {
-        // ---- cached frame: gather the selected views' maps, texels and cameras instead of computing them.  Level 0 / level 1 maps,
-        // the non-final levels' texels and the cameras (everything the chain needs first) on the caller's stream; the level-2 map
-        // and the last level's texels, two thirds of the bytes and needed only by the final render, on the side lane.  The camera-only
-        // preparation reads the gathered rows, so it runs as the level loop's own launches (prep_carried stays 0).
-        GatherJob main_job, side_job;
-        memset(&main_job, 0, sizeof(main_job));
-        memset(&side_job, 0, sizeof(side_job));
-        main_job.V = side_job.V = cache->V;
-        main_job.view_idx = side_job.view_idx = view_idx;
-        main_job.exts = cache->exts; main_job.ixts = cache->ixts;
-        main_job.dst_exts = ws + P.cam_exts; main_job.dst_ixts = ws + P.cam_ixts;
-        auto add = [](GatherJob& J, const float* src, float* dst, long long floats_per_view) {
-            J.seg[J.nseg++] = GatherSeg{reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), floats_per_view / 4};
-        };
-        add(main_job, cache->feat_l0, f[0], (long long)fh[0] * fw[0] * 32);
-        add(main_job, cache->feat_l1, f[1], (long long)fh[1] * fw[1] * 16);
-        bool uses2 = c.num >= 3;                      // level_2 feeds a third level's cost volume, or IS a render's texels (stride 12);
-        for (int i = 0; i < c.num; ++i)               // a render from the plain map reads its own texel image instead
-            uses2 = uses2 || (P.L[i].render && c.render_im_feat_level[i] == 2 && P.tex2);
-        if (uses2) add(side_job, cache->feat_l2, f[2], (long long)a->H * a->W * cache->l2_stride);
-        for (int i = 0; i < c.num; ++i) {
-            const LevelPlan& L = P.L[i];
-            if (!L.render || (c.render_im_feat_level[i] == 2 && P.tex2)) continue;
-            add(i + 1 < c.num ? main_job : side_job, cache->tex[i], ws + L.tex, (long long)L.Hr * L.Wr * 4 * ((L.F + 3) / 4));
-        }
-#ifndef ENERF_EMU
-        if (!(a->options && a->options->single_stream) && side_job.nseg > 0) lane = side_lane(st);
-        if (lane != nullptr) {
-            lane_busy = std::unique_lock<std::mutex>(lane->busy);
-            hipEventRecord(lane->trunk, st);           // the lane starts behind the previous frame and the producer of view_idx
-            hipStreamWaitEvent(lane->stream, lane->trunk, 0);
-            launch_gather_sources(main_job, n_img, st);
-            launch_gather_sources(side_job, n_img, lane->stream);
-            hipEventRecord(lane->l1, lane->stream);
-            hipEventRecord(lane->l2, lane->stream);
-            forked = true; joined[1] = 1; joined[2] = 0;       // (level 1 came with the caller's stream)
-        } else
-#endif
-        {
-            for (int s = 0; s < side_job.nseg; ++s) main_job.seg[main_job.nseg++] = side_job.seg[s];
-            launch_gather_sources(main_job, n_img, st);
-        }
-        rc = check_launch("forward_cached: gather");
-        if (rc != ENERF_OK) return bail(rc);
-    } else if (P.hip_feats) {
-        const int l2s = P.tex2 ? 12 : 8;
-        auto fstage = [&](int stage, enerf_stream_t s) {
-            const bool first = stage == ENERF_FEAT_ALL || stage == ENERF_FEAT_TRUNK;
-            return feature_net_stage_job(a->feature_net_packed, a->src_inps, n_img, a->H, a->W, f[0], f[1], f[2], l2s,
-                                         ws + P.featnet_ws, P.featnet_ws_bytes, stage, a->options, (hipStream_t)s,
-                                         first && job.nblocks > 0 ? &job : nullptr, first ? &prep_carried : nullptr);
-        };
-#ifndef ENERF_EMU
-        if (!(a->options && a->options->single_stream)) lane = side_lane(st);
-        if (lane != nullptr) {
-            lane_busy = std::unique_lock<std::mutex>(lane->busy);
-            rc = fstage(ENERF_FEAT_TRUNK, stream);
-            if (rc != ENERF_OK) return rc;
-            hipEventRecord(lane->trunk, st);
-            hipStreamWaitEvent(lane->stream, lane->trunk, 0);
-            rc = fstage(ENERF_FEAT_LEVEL1, (enerf_stream_t)lane->stream);
-            hipEventRecord(lane->l1, lane->stream);
-            // The last stage (lat0 + smooth0 -> render texels) is needed only by the final render.  Enqueued here (default) it
-            // shares the chip with level 0; GATED (enerf_options_t.side_gate >= 2) it is enqueued later, from inside the last
-            // level's cost regularisation, behind an event, to run beside that level's small deep layers instead.  Measured in
-            // round 3 (profiles/r03_ab_side_gate.txt): gating LOSES 1-2 % on all three workloads — the early start wins.
-            gate_mode = a->options ? a->options->side_gate : 0;
-            if (gate_mode == 0) gate_mode = 1;
-            const int lastl = c.num - 1;
-            const bool gateable = c.num >= 2 && P.tex2 && c.render_if[lastl] && c.render_im_feat_level[lastl] == 2;
-            for (int l = 0; l < lastl && gateable; ++l)                       // nobody before the last level may need level_2
-                if (c.render_if[l] && c.render_im_feat_level[l] == 2) gate_mode = 1;
-            if (!gateable) gate_mode = 1;
-            if (gate_mode == 1) {
-                if (rc == ENERF_OK) rc = fstage(ENERF_FEAT_LEVEL2, (enerf_stream_t)lane->stream);
-                hipEventRecord(lane->l2, lane->stream);
-                stage2_enqueued = true;
-            }
-            forked = true; joined[1] = joined[2] = 0;
-            if (rc != ENERF_OK) return bail(rc);      // never leave the lane un-joined
-        } else
-#endif
-        {
-            rc = fstage(ENERF_FEAT_ALL, stream);
-            if (rc != ENERF_OK) return rc;
-        }
-    } else {
-        for (int l = 0; l < c.num; ++l)   // the levels that feed a cost volume (texels are packed from NCHW below)
-            launch_channels_last(a->feats_nchw[l], f[l], n_img, fc[l], (long long)fh[l] * fw[l], fc[l], st);
-    }
-    mark(ENERF_STAGE_FEATURE_NET);
-
-#ifndef ENERF_EMU
-    // deferred enqueue of the FeatureNet's last stage on the side lane, behind an event recorded on the caller's stream NOW
-    struct GateCtx { void* self; };
-    auto enqueue_stage2 = [&]() {
-        if (stage2_enqueued || lane == nullptr) return;
-        hipEventRecord(lane->fork, st);                               // "the chain has reached this point"
-        hipStreamWaitEvent(lane->stream, lane->fork, 0);
-        const int l2s = P.tex2 ? 12 : 8;
-        stage2_rc = enerf_feature_net_stage(a->feature_net_packed, a->src_inps, n_img, a->H, a->W, f[0], f[1], f[2], l2s,
-                                            ws + P.featnet_ws, P.featnet_ws_bytes, ENERF_FEAT_LEVEL2, a->options,
-                                            (enerf_stream_t)lane->stream);
-        hipEventRecord(lane->l2, lane->stream);
-        stage2_enqueued = true;
-    };
-    auto* enq_ptr = &enqueue_stage2;
-    CostRegHook hook = {[](void* ctx) { (*static_cast<decltype(enq_ptr)>(ctx))(); }, enq_ptr, gate_mode == 4 ? 2 : 0};
-    if (forked && gate_mode != 1) stage2_enqueued = false;
-#endif
-    const float *pdepth = nullptr, *pstd = nullptr, *pnf = nullptr;
-    const float *pending_prob = nullptr, *pending_dv = nullptr;       // a depth regression deferred into the next level's prep
-    int pending_D = 0, pending_inv = 0;
-    int hp = 0, wp = 0;
-    for (int i = 0; i < c.num; ++i) {
-        const LevelPlan& L = P.L[i];
-        float *proj = ws + L.proj, *dv = ws + L.dv, *nf = ws + L.nf, *vol = ws + L.vol, *feat3d = ws + L.feat3d;
-        float *prob = ws + L.prob, *depth = ws + L.depth;
-        float* std = L.render ? a->std[i] : ws + L.std;
-        float* dmvs = L.render ? a->depth_mvs[i] : nullptr;
-        // the previous level's depth regression rides in this level's prep launch when that level is not rendered (its depth /
-        // std are then only this level's inputs): one launch instead of two on the critical chain between the levels
-        bool prep_done = false;
-        if (pending_prob != nullptr) {
-            // (the level's projection matrices are already there when the frame's first launch carried the preparation job)
-            prep_done = launch_regress_and_values(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->S, (float)c.im_feat_scale[i],
-                                                  (float)c.volume_scale[i], prep_carried && i < 3 ? nullptr : proj, pending_prob, pending_dv, pnf, pending_D, hp, wp,
-                                                  pending_inv, const_cast<float*>(pdepth), const_cast<float*>(pstd), a->B, L.D,
-                                                  L.h, L.w, c.depth_inv[i], dv, nf, st);
-            if (!prep_done)         // shape outside the fused kernel's limits: the two separate launches
-                launch_depth_regression(pending_prob, pending_dv, a->B, pending_D, hp, wp, pending_inv,
-                                        const_cast<float*>(pdepth), const_cast<float*>(pstd), nullptr, st);
-            pending_prob = nullptr;
-        }
-        if (i == 0 && prep_carried) prep_done = true;                  // level 0: planes + matrices came with the first launch
-        if (!prep_done)
-            rc = enerf_level_prep(src_ixts, src_exts, a->tar_ixt, a->tar_ext, a->B, a->S, (float)c.im_feat_scale[i],
-                                  (float)c.volume_scale[i], proj, a->near_far, pdepth, pstd, pnf, L.D, L.h, L.w, hp, wp,
-                                  c.depth_inv[i], dv, nf, stream);
-        else
-            rc = check_launch("level_prep");
-        if (rc != ENERF_OK) return bail(rc);
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_PREP));
-        need_level(i);                                                 // level i's source maps (side lane for i >= 1)
-        // the volume goes to conv0 as channel-quad planes when conv0 runs on the asynchronously staged kernel (one quad per pass)
-        const int vol_planar = cost_reg_wants_planar_volume(resolve_options(a->options), L.C, a->B, L.D, L.h, L.w) ? 1 : 0;
-        if (!vol_planar)
-            rc = enerf_build_feature_volume(f[i], proj, dv, a->B, a->S, L.C, L.Hs, L.Ws, L.D, L.h, L.w, vol, stream);
-        else {      // same argument checks as the C entry (shapes come from the validated plan; the 32-bit limits are re-checked)
-            REQUIRE((long long)a->B * a->S * L.Hs * L.Ws * L.C < (1LL << 32) && (long long)L.Hs * L.Ws < (1LL << 23) &&
-                    (long long)a->B * L.D * L.h * L.w * (L.C / 4) < (1LL << 31) && (long long)L.h * L.w < (1LL << 23) &&
-                    (long long)a->B * L.D <= 65535 && (long long)a->B * L.D * L.h < (1LL << 23) && L.w < (1 << 23),
-                    "forward: level %d volume too large for 32-bit indices / the grid-carried voxel decomposition", i);
-            launch_feature_volume(f[i], proj, dv, a->B, a->S, L.C, L.Hs, L.Ws, L.D, L.h, L.w, vol, st, 1);
-            rc = check_launch("build_feature_volume");
-        }
-        if (rc != ENERF_OK) return bail(rc);
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_VOLUME));
-        const CostRegHook* hk = nullptr;
-#ifndef ENERF_EMU
-        if (!stage2_enqueued && i == c.num - 1) {
-            if (gate_mode == 3) enqueue_stage2(); else hk = &hook;
-        }
-#endif
-        rc = cost_reg_run(a->cost_reg_packed[i], L.C, i != 0, vol, vol_planar, a->B, L.D, L.h, L.w, feat3d, prob, ws + P.costreg_ws,
-                          P.costreg_ws_bytes, a->options, st, hk);
-#ifndef ENERF_EMU
-        if (!stage2_enqueued && i == c.num - 1) enqueue_stage2();     // (an error path inside cost_reg skipped the hook)
-        if (rc == ENERF_OK && stage2_rc != ENERF_OK) rc = stage2_rc;
-#endif
-        if (rc != ENERF_OK) return bail(rc);
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_COST_REG));
-        const bool defer_regression = !L.render && i + 1 < c.num && !(a->options && a->options->fuse_depth_prep == 1);
-        if (defer_regression) { pending_prob = prob; pending_dv = dv; pending_D = L.D; pending_inv = c.depth_inv[i]; }
-        else launch_depth_regression(prob, dv, a->B, L.D, L.h, L.w, c.depth_inv[i], depth, std, dmvs, st);
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_DEPTH_REG));
-        pdepth = depth; pstd = std; pnf = nf; hp = L.h; wp = L.w;
-        if (!L.render) continue;
-
-        // ---- texels: unpreprocess + cat (network.py:28-34) as the channels-last gather source ----
-        const int fl = c.render_im_feat_level[i];
-        const int TEX = 4 * ((L.F + 3) / 4);
-        const float* tex;
-        if (cache == nullptr || (fl == 2 && P.tex2)) need_level(fl);   // the texel source (joined here, inside the texel stage)
-        // a non-final level's render is a leaf of the frame: fork it (its inputs are complete on the caller's stream here)
-        bool render_forked = false;
-        enerf_stream_t rs = stream;
-#ifndef ENERF_EMU
-        if (forked && i + 1 < c.num && !L.masked) {
-            if (render_forks > 0) hipStreamWaitEvent(lane->rstream, lane->done, 0);   // (ordering only: same stream anyway)
-            hipEventRecord(lane->fork, st);
-            hipStreamWaitEvent(lane->rstream, lane->fork, 0);
-            rs = (enerf_stream_t)lane->rstream; cur = lane->rstream; render_forked = true; ++render_forks;
-        }
-#endif
-        if (fl == 2 && P.tex2) tex = f[2];
-        else if (cache != nullptr) {                                   // gathered with the maps; the last level's on the side lane
-            if (i + 1 == c.num) need_level(2);
-            tex = ws + L.tex;
-        } else {
-            float* t = ws + L.tex;
-            if (P.hip_feats)
-                rc = enerf_pack_texels_cl(f[fl], fc[fl], a->src_inps, a->H, a->W, L.Hr, L.Wr, TEX, n_img, t, rs);
-            else
-                rc = enerf_pack_img_feat_rgb(a->feats_nchw[fl], fc[fl], fh[fl], fw[fl], a->src_inps, a->H, a->W, L.Hr, L.Wr,
-                                             TEX, n_img, t, rs);
-            if (rc != ENERF_OK) return bail(rc);
-            tex = t;
-        }
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_TEXELS));
-
-        // ---- rays: the batch's, or the full image generated here (enerf_utils.py:61-71) ----
-        const float* rays8 = a->rays[i];
-        if (rays8 == nullptr) {
-            float* r = ws + L.rays;
-            rc = enerf_gen_rays(a->tar_ext, a->tar_ixt, a->B, L.Hr, L.Wr, (float)c.render_scale[i], r, rs);
-            if (rc != ENERF_OK) return bail(rc);
-            rays8 = r;
-        }
-        // ---- build_rays + render_rays (utils.py:390-420, network.py:24-43), one launch ----
-        enerf_render_args_t ra;
-        memset(&ra, 0, sizeof(ra));
-        ra.tex = tex; ra.vol = feat3d; ra.src_exts = src_exts; ra.src_ixts = src_ixts; ra.tar_ext = a->tar_ext;
-        ra.packed = a->nerf_packed[i];
-        ra.rgb = a->rgb[i]; ra.depth = a->depth[i]; ra.weights = a->weights[i];
-        ra.B = a->B; ra.N = (int)L.n_rays; ra.S = a->S; ra.n_samples = L.Ns; ra.depth_inv = c.depth_inv[i];
-        ra.Hr = L.Hr; ra.Wr = L.Wr; ra.F = L.F; ra.D = L.D; ra.h = L.h; ra.w = L.w; ra.white_bkgd = c.white_bkgd;
-        ra.render_scale = (float)c.render_scale[i];
-        ra.rays8 = rays8; ra.depth_map = depth; ra.std_map = std; ra.nf_map = nf; ra.map_h = L.h; ra.map_w = L.w;
-        ra.options = a->options;
-        // A forked render is a leaf that shares the device with the next level.  As one persistent block per compute unit (130 KB of
-        // LDS each at C = 32) it kept the next level's LDS-staged kernels off every CU until its blocks exited; on HALF of the CUs,
-        // with the balanced tile deal, the next level starts at once and the leaf ends under its small layers: lego 543 -> 558
-        // frames/s (64 blocks 509, 96: 556, 128: 558, 160: 546, all 256: 535; profiles/r06_ab_bg_render_blocks.txt)
-#ifndef ENERF_BG_RENDER_DIV
-#define ENERF_BG_RENDER_DIV 2        // a forked render's persistent blocks = compute units / this; 0 = one per compute unit
-#endif
-        if (render_forked && ENERF_BG_RENDER_DIV > 0) ra.max_blocks = device_cu_count() / ENERF_BG_RENDER_DIV;
-        if (L.masked) {
-            ra.ray_index = ray_index; ra.ray_count = ray_count; ra.scatter_rgb = 1;
-            zero_async(a->rgb[i], (size_t)L.n_rays * 3 * sizeof(float), (hipStream_t)rs);      // torch.zeros_like(...), network_human.py:103
-        }
-        rc = enerf_render_rays(&ra, rs);
-        if (rc != ENERF_OK) return bail(rc);
-        mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_RENDER));
-#ifndef ENERF_EMU
-        if (render_forked) { hipEventRecord(lane->done, lane->rstream); cur = st; }
-#endif
-        (void)render_forked;
-    }
-#ifndef ENERF_EMU
-    if (render_forks > 0) hipStreamWaitEvent(st, lane->done, 0);       // join the forked renders
-#endif
-    need_level(1); need_level(2);        // the caller's stream never returns ahead of the side lane
-    return check_launch("forward");
-}
-}  // namespace
-
-extern "C" {
-
 int enerf_forward(const enerf_frame_args_t* a, enerf_stream_t stream) { return run_frame(a, nullptr, nullptr, stream); }
 
 size_t enerf_forward_cached_workspace_bytes(const enerf_frame_args_t* a, const enerf_source_cache_t* cache) {
@@ -732,26 +767,23 @@ int enerf_forward_cached(const enerf_frame_args_t* a, const enerf_source_cache_t
 }
 
 // ---- the cache itself: sizes for a cascade, and the build (FeatureNet + texel packing over the V views, <= 4 at a time) ----
-int enerf_source_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, int* l2_stride, long long* floats) {
-    REQUIRE(cas && l2_stride && floats, "source_cache_sizes: null pointer");
+int enerf_source_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, int* l2_stride_out, long long* floats) {
+    REQUIRE(cas && l2_stride_out && floats, "source_cache_sizes: null pointer");
     const enerf_cascade_t& c = *cas;
     REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "source_cache_sizes: cas_config.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
     REQUIRE(V >= 1 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "source_cache_sizes: bad shape V=%d H=%d W=%d (H and W divisible by 4)", V, H, W);
-    const int l2s = cascade_tex2(c) ? 12 : 8;
-    const int fh[3] = {H / 4, H / 2, H}, fw[3] = {W / 4, W / 2, W}, fc[3] = {32, 16, 8};
-    *l2_stride = l2s;
-    for (int l = 0; l < 3; ++l) floats[l] = (long long)V * fh[l] * fw[l] * (l == 2 ? l2s : fc[l]);
+    const int tex2 = cascade_tex2(c);
+    const FeatDims fd(H, W);
+    *l2_stride_out = l2_stride(tex2);
+    for (int l = 0; l < 3; ++l) floats[l] = (long long)V * fd.pixels(l) * (l == 2 ? l2_stride(tex2) : fd.c[l]);
     for (int i = 0; i < ENERF_MAX_LEVELS; ++i) {
         floats[3 + i] = 0;
         if (i >= c.num || !c.render_if[i]) continue;
-        const int fl = c.render_im_feat_level[i];
-        REQUIRE(fl >= 0 && fl <= 2 && fc[fl] == c.nerf_model_feat_ch[i],
-                "source_cache_sizes: render_im_feat_level[%d]=%d does not have nerf_model_feat_ch=%d channels", i, fl, c.nerf_model_feat_ch[i]);
         const int Hr = scaled(H, c.render_scale[i]), Wr = scaled(W, c.render_scale[i]);
-        REQUIRE(fh[fl] == Hr && fw[fl] == Wr, "source_cache_sizes: level %d renders at %dx%d but feature level_%d is %dx%d "
-                "(the HIP FeatureNet path needs render_scale == im_ibr_scale)", i, Hr, Wr, fl, fh[fl], fw[fl]);
-        if (fl == 2 && l2s == 12) continue;
-        floats[3 + i] = (long long)V * Hr * Wr * 4 * ((c.nerf_model_feat_ch[i] + 3 + 3) / 4);
+        const int rc = check_render_feat("source_cache_sizes", c, i, fd, Hr, Wr, true);
+        if (rc != ENERF_OK) return rc;
+        if (renders_from_l2(c, i, tex2)) continue;
+        floats[3 + i] = (long long)V * Hr * Wr * tex_stride(c.nerf_model_feat_ch[i] + 3);
     }
     floats[6] = (long long)V * 16;
     floats[7] = (long long)V * 9;
@@ -776,19 +808,19 @@ int enerf_source_cache_build(const enerf_source_cache_t* cache, const float* src
     if (rc != ENERF_OK) return rc;
     if (workspace_bytes < enerf_source_cache_build_workspace_bytes(H, W))
         return fail(ENERF_EWORKSPACE, "source_cache_build: workspace too small");
-    const int fh[3] = {H / 4, H / 2, H}, fw[3] = {W / 4, W / 2, W}, fc[3] = {32, 16, 8};
+    const FeatDims fd(H, W);
     float* maps[3] = {cache->feat_l0, cache->feat_l1, cache->feat_l2};
     for (int v0 = 0; v0 < V; v0 += chunk) {
         const int n = V - v0 < chunk ? V - v0 : chunk;
         const float* img = src_inps + (size_t)v0 * 3 * H * W;
         float* m[3];
-        for (int l = 0; l < 3; ++l) m[l] = maps[l] + (size_t)v0 * fh[l] * fw[l] * (l == 2 ? l2s : fc[l]);
+        for (int l = 0; l < 3; ++l) m[l] = maps[l] + (size_t)v0 * fd.pixels(l) * (l == 2 ? l2s : fd.c[l]);
         rc = enerf_feature_net(feature_net_packed, img, n, H, W, m[0], m[1], m[2], l2s, workspace, workspace_bytes, options, stream);
         if (rc != ENERF_OK) return rc;
         for (int i = 0; i < cas->num; ++i) {
             if (floats[3 + i] == 0) continue;
-            const int fl = cas->render_im_feat_level[i], TEX = 4 * ((fc[fl] + 3 + 3) / 4);
-            rc = enerf_pack_texels_cl(m[fl], fc[fl], img, H, W, fh[fl], fw[fl], TEX, n, cache->tex[i] + (size_t)v0 * fh[fl] * fw[fl] * TEX, stream);
+            const int fl = cas->render_im_feat_level[i], TEX = tex_stride(fd.c[fl] + 3);
+            rc = enerf_pack_texels_cl(m[fl], fd.c[fl], img, H, W, fd.h[fl], fd.w[fl], TEX, n, cache->tex[i] + (size_t)v0 * fd.pixels(fl) * TEX, stream);
             if (rc != ENERF_OK) return rc;
         }
     }

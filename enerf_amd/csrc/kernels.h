@@ -171,7 +171,7 @@ void launch_select_views(const float* cam_points, int V, const float* c2w, int k
 void launch_gather_views(const float* inps, const float* exts, const float* ixts, const int* idx, int k, int H, int W,
                          float* src_inps, float* src_exts, float* src_ixts, hipStream_t st);
 
-// ---- frame.hip (mask_at_box compaction; the whole-frame driver enerf_forward lives there too) ---------
+// ---- frame.hip (mask_at_box compaction; the frame driver — FrameRun's stages, run_frame — and its side lane, side_lane.h, live there too) ----
 size_t mask_compact_workspace_bytes(long long n);
 void launch_mask_compact(const void* mask, int elem_bytes, long long n, int* index, int* count, void* workspace,
                          hipStream_t st);

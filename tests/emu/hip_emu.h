@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -207,6 +208,36 @@ inline void launch(bool lockstep, dim3 grid, dim3 block, size_t shmem, F&& kerne
     for (auto& t : pool) t.join();
 }
 
+// Launch trace (tests/emu_lib.py emu_trace): while it is on, every ENERF_LAUNCH / ENERF_LAUNCH_SIMPLE of the calling thread appends
+//   launch \t kernel \t gx \t gy \t gz \t stream handle
+// and the frame's side lane (csrc/side_lane.h) its event records and waits
+//   record | wait \t event \t stream name \t stream handle
+// one line each, in enqueue order.  Off (the default) it costs one thread-local flag test per launch.
+// ENERF_EMU_TRACE tells the kernel sources that this header has the trace: they also build against an emulator header without
+// it (the lane's verbs and the trace exports of capi.hip then compile to nothing).
+#define ENERF_EMU_TRACE 1
+struct Trace { bool on = false; std::string text; };
+inline Trace& trace() {
+    static thread_local Trace t;
+    return t;
+}
+inline void trace_launch(const char* kern, dim3 grid, const void* stream) {
+    Trace& t = trace();
+    if (!t.on) return;
+    char buf[64];
+    snprintf(buf, sizeof(buf), "\t%u\t%u\t%u\t%llx\n", grid.x, grid.y, grid.z, (unsigned long long)(uintptr_t)stream);
+    t.text += "launch\t";
+    t.text += kern;
+    t.text += buf;
+}
+inline void trace_sync(const char* verb, const char* event, const char* stream_name, const void* stream) {
+    Trace& t = trace();
+    if (!t.on) return;
+    char buf[96];
+    snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%llx\n", verb, event, stream_name, (unsigned long long)(uintptr_t)stream);
+    t.text += buf;
+}
+
 struct TidProxy { unsigned y = 0, z = 0; struct X { operator unsigned() const { return ctx()->tid; } } x; };
 struct BidProxy {
     struct X { operator unsigned() const { return ctx()->blockIdx.x; } } x;
@@ -330,6 +361,8 @@ inline int atomicMin(int* p, int v) {
 }
 
 #define ENERF_LAUNCH(kern, grid, block, shmem, stream, ...) \
-    emu::launch(true, dim3(grid), dim3(block), (size_t)(shmem), [&]() { kern(__VA_ARGS__); })
+    (emu::trace_launch(#kern, dim3(grid), (stream)), \
+     emu::launch(true, dim3(grid), dim3(block), (size_t)(shmem), [&]() { kern(__VA_ARGS__); }))
 #define ENERF_LAUNCH_SIMPLE(kern, grid, block, shmem, stream, ...) \
-    emu::launch(false, dim3(grid), dim3(block), (size_t)(shmem), [&]() { kern(__VA_ARGS__); })
+    (emu::trace_launch(#kern, dim3(grid), (stream)), \
+     emu::launch(false, dim3(grid), dim3(block), (size_t)(shmem), [&]() { kern(__VA_ARGS__); }))

@@ -26,3 +26,34 @@ def emu_cu_count(lib: EnerfLib, n: int):
         yield
     finally:
         lib.dll.emu_set_cu_count(EMU_DEFAULT_CUS)
+
+
+@contextlib.contextmanager
+def emu_trace(lib: EnerfLib, main_stream: int = 0):
+    """Record what the calling thread enqueues inside the block (tests/emu/hip_emu.h); yields a list that is filled when the block
+    ends, in enqueue order, with
+        ("launch", kernel, (gx, gy, gz), stream)      every ENERF_LAUNCH / ENERF_LAUNCH_SIMPLE; kernel as written at the call site
+        ("record", event, stream)                     the frame's side lane (csrc/side_lane.h): event recorded on stream
+        ("wait", event, stream)                       stream waits for event
+    Streams are "main" (the handle ``main_stream``: the caller's), "side" and "render" (the lane's), or the handle in hex."""
+    import ctypes as C
+    dll = lib.dll
+    dll.emu_trace_read.restype = C.c_longlong
+    dll.emu_trace_read.argtypes = [C.c_char_p, C.c_longlong]
+    out = []
+    dll.emu_trace_reset(1)
+    try:
+        yield out
+    finally:
+        n = dll.emu_trace_read(None, 0)
+        buf = C.create_string_buffer(max(int(n), 1))
+        dll.emu_trace_read(buf, n)
+        dll.emu_trace_reset(0)
+        rows = [ln.split("\t") for ln in buf.raw[:n].decode().splitlines()]
+        names = {"%x" % main_stream: "main"}
+        names.update({r[3]: r[2] for r in rows if r[0] != "launch"})
+        for r in rows:
+            if r[0] == "launch":
+                out.append(("launch", r[1], (int(r[2]), int(r[3]), int(r[4])), names.get(r[5], r[5])))
+            else:
+                out.append((r[0], r[1], r[2]))

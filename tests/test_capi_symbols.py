@@ -26,7 +26,8 @@ def test_hip_library_builds_and_exports_all_symbols():
     out = subprocess.run(["nm", "-D", "--defined-only", LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r"\bT (enerf_[a-z0-9_]+)", out))
     assert set(_declared()) <= exported, set(_declared()) - exported
-    assert "emu_set_cu_count" not in out                  # the emulator's CU-count seam (tests/emu_lib.py) stays out of the product
+    # the emulator's seams (tests/emu_lib.py: the CU count, the launch trace) stay out of the product
+    assert not re.findall(r"\b\w+ (_?emu_\w*)", out)
     lib = EnerfLib(LIB_PATH)                              # dlopen + ABI version; no compute calls here
     from enerf_amd.lib import ABI_VERSION
     assert lib.dll.enerf_abi_version() == ABI_VERSION == 11
