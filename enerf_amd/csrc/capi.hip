@@ -78,31 +78,58 @@ int check_launch(const char* what) {
 namespace {
 
 // ---- cost-reg layer table ------------------------------------------------------------------------
-struct LayerSpec { int idx, cin, cout, kind, relu, bn; };
-// returns number of layers; the fused heads (8 -> 8+1) are appended last with idx = -1
+// buffers a layer reads / writes: the caller's volume and outputs, and the workspace's activations in the order they are carved
+enum { kVol = -1, kNoBuf = -2, kFeatProb = -3, kC0 = 0, kC1, kC2, kC3, kC4, kY9, kY11, kC5, kC6, kY7, kNumBufs };
+// idx: the reference's conv number (-1: the fused heads, 8 -> 8 + 1, last); div: the input volume is (D, h, w) / div
+struct LayerSpec { int idx, cin, cout, kind, relu, in, res, out, div; };
 int costreg_layers(int cin0, int full, LayerSpec* L) {
     int n = 0;
-    L[n++] = {0, cin0, 8, kConvS1, 1, 1};
-    L[n++] = {1, 8, 16, kConvS2, 1, 1};
-    L[n++] = {2, 16, 16, kConvS1, 1, 1};
-    L[n++] = {3, 16, 32, kConvS2, 1, 1};
-    L[n++] = {4, 32, 32, kConvS1, 1, 1};
+    L[n++] = {0, cin0, 8, kConvS1, 1, kVol, kNoBuf, kC0, 1};
+    L[n++] = {1, 8, 16, kConvS2, 1, kC0, kNoBuf, kC1, 1};
+    L[n++] = {2, 16, 16, kConvS1, 1, kC1, kNoBuf, kC2, 2};
+    L[n++] = {3, 16, 32, kConvS2, 1, kC2, kNoBuf, kC3, 2};
+    L[n++] = {4, 32, 32, kConvS1, 1, kC3, kNoBuf, kC4, 4};
     if (full) {
-        L[n++] = {5, 32, 64, kConvS2, 1, 1};
-        L[n++] = {6, 64, 64, kConvS1, 1, 1};
-        L[n++] = {7, 64, 32, kConvT2, 0, 1};
+        L[n++] = {5, 32, 64, kConvS2, 1, kC4, kNoBuf, kC5, 4};
+        L[n++] = {6, 64, 64, kConvS1, 1, kC5, kNoBuf, kC6, 8};
+        L[n++] = {7, 64, 32, kConvT2, 0, kC6, kC4, kY7, 8};                     // conv4 + conv7
     }
-    L[n++] = {9, 32, 16, kConvT2, 0, 1};
-    L[n++] = {11, 16, 8, kConvT2, 0, 1};
-    L[n++] = {-1, 8, 9, kConvS1, 0, 0};
+    L[n++] = {9, 32, 16, kConvT2, 0, full ? kY7 : kC4, kC2, kY9, 4};            // conv2 + conv9
+    L[n++] = {11, 16, 8, kConvT2, 0, kY9, kC0, kY11, 2};                        // conv0 + conv11
+    L[n++] = {-1, 8, 9, kConvS1, 0, kY11, kNoBuf, kFeatProb, 1};                // feat_conv ++ depth_conv
     return n;
 }
-bool layer_pk8(const LayerSpec& s) { return s.kind == kConvS1 && (s.cout == 8 || s.idx < 0); }   // conv0, fused heads
-bool layer_t2pair(const LayerSpec& s) { return s.kind == kConvT2 && s.cin == 16 && s.cout == 8; }   // conv11
-long long layer_floats(const LayerSpec& s) {
-    return conv3d_packed_floats(s.cin, s.cout, s.kind) + 2 * cdiv(s.cout, 16) * 16 +
-           (layer_pk8(s) ? conv3d_pk8_packed_floats(s.cin) + conv3d_b4_packed_floats(s.cin) : 0) +
-           (layer_t2pair(s) ? conv3d_t2_pair_floats() : 0);
+// conv0 and the fused heads carry the pk8 and b4 images besides their own
+Conv3dImage layer_image(const LayerSpec& s) { return conv3d_layer_image(s.cin, s.cout, s.kind, s.kind == kConvS1 && (s.cout == 8 || s.idx < 0)); }
+// floats of every workspace buffer, in carve order; returns how many there are
+int costreg_buffers(int full, long long n0, long long* floats) {
+    const long long n1 = n0 / 8, n2 = n1 / 8, n3 = n2 / 8;
+    const long long f[kNumBufs] = {n0 * 8, n1 * 16, n1 * 16, n2 * 32, n2 * 32, n1 * 16, n0 * 8, n3 * 64, n3 * 64, n2 * 32};
+    const int n = full ? kNumBufs : kC5;
+    for (int i = 0; i < n; ++i) floats[i] = f[i];
+    return n;
+}
+// What one enerf_cost_reg call runs: every layer's route, decided before anything is launched, and the two layout hand-offs that
+// follow from the routes — the cost volume (warp -> conv0) and conv11's output (-> fused heads) travel as channel-quad planes exactly
+// when both ends are kernels that speak that layout.
+struct CostRegPlan {
+    int n;
+    LayerSpec spec[12];
+    Conv3dRoute route[12];
+    bool vol_planar_ok;      // conv0 can read a quad-planar volume
+    bool heads_planar;       // conv11 writes, and the heads read, quad planes
+};
+CostRegPlan cost_reg_plan(int in_channels, int full, int B, int D, int h, int w, const Options& opt, int cus) {
+    CostRegPlan P;
+    P.n = costreg_layers(in_channels, full, P.spec);
+    for (int i = 0; i < P.n; ++i) {
+        const LayerSpec& s = P.spec[i];
+        P.route[i] = conv3d_route(conv3d_layer_of(layer_image(s), s.cin, s.cout, s.kind), s.res != kNoBuf, s.out == kFeatProb, B,
+                                  D / s.div, h / s.div, w / s.div, opt, cus);
+    }
+    P.vol_planar_ok = conv3d_route_planar_in(P.route[0]);
+    P.heads_planar = conv3d_route_planar_out(P.route[P.n - 2]) && conv3d_route_planar_in(P.route[P.n - 1]);
+    return P;
 }
 }  // namespace
 
@@ -177,45 +204,42 @@ long long enerf_cost_reg_packed_floats(int in_channels, int full) {
     LayerSpec L[12];
     int n = costreg_layers(in_channels, full, L);
     long long t = 0;
-    for (int i = 0; i < n; ++i) t += layer_floats(L[i]);
+    for (int i = 0; i < n; ++i) t += layer_image(L[i]).floats;
     return t;
 }
 int enerf_cost_reg_pack(const enerf_costreg_raw_t* raw, float* packed, enerf_stream_t stream) {
     REQUIRE(raw && packed, "cost_reg_pack: null pointer");
     REQUIRE(raw->in_channels == 8 || raw->in_channels == 16 || raw->in_channels == 32, "cost_reg_pack: in_channels");
+    hipStream_t st = (hipStream_t)stream;
     LayerSpec L[12];
     int n = costreg_layers(raw->in_channels, raw->full, L);
     float* p = packed;
     for (int i = 0; i < n; ++i) {
         const LayerSpec& s = L[i];
-        long long wf = conv3d_packed_floats(s.cin, s.cout, s.kind);
-        int cp = cdiv(s.cout, 16) * 16;
+        const Conv3dImage im = layer_image(s);
+        const float *w = raw->feat_conv_w, *wd = raw->depth_conv_w;         // the fused heads: no BN (scale / shift = 1 / 0)
         if (s.idx >= 0) {
             const enerf_conv_bn_t& c = raw->conv[s.idx];
             REQUIRE(c.w && c.bn_weight && c.bn_bias && c.bn_mean && c.bn_var, "cost_reg_pack: conv%d missing", s.idx);
-            launch_conv3d_pack(c.w, nullptr, s.cout, c.bn_weight, c.bn_bias, c.bn_mean, c.bn_var, 1e-5f, s.cin, s.cout,
-                               s.kind, p, p + wf, p + wf + cp, (hipStream_t)stream);
-            if (layer_t2pair(s)) launch_conv3d_t2_pair_pack(p, p + wf + 2 * cp, (hipStream_t)stream);   // from the image just packed
-            if (layer_pk8(s)) {
-                launch_conv3d_pk8_pack(c.w, nullptr, s.cin, p + wf + 2 * cp, (hipStream_t)stream);
-                launch_conv3d_b4_pack(c.w, nullptr, s.cin, p + wf + 2 * cp + conv3d_pk8_packed_floats(s.cin), (hipStream_t)stream);
-            }
+            w = c.w; wd = nullptr;
+            launch_conv3d_pack(c.w, nullptr, s.cout, c.bn_weight, c.bn_bias, c.bn_mean, c.bn_var, 1e-5f, s.cin, s.cout, s.kind,
+                               p + im.w, p + im.scale, p + im.shift, st);
         } else {
-            REQUIRE(raw->feat_conv_w && raw->depth_conv_w, "cost_reg_pack: heads missing");
-            launch_conv3d_pack(raw->feat_conv_w, raw->depth_conv_w, 8, nullptr, nullptr, nullptr, nullptr, 1e-5f, s.cin,
-                               s.cout, s.kind, p, p + wf, p + wf + cp, (hipStream_t)stream);
-            launch_conv3d_pk8_pack(raw->feat_conv_w, raw->depth_conv_w, s.cin, p + wf + 2 * cp, (hipStream_t)stream);
-            launch_conv3d_b4_pack(raw->feat_conv_w, raw->depth_conv_w, s.cin, p + wf + 2 * cp + conv3d_pk8_packed_floats(s.cin),
-                                  (hipStream_t)stream);
+            REQUIRE(w && wd, "cost_reg_pack: heads missing");
+            launch_conv3d_pack(w, wd, 8, nullptr, nullptr, nullptr, nullptr, 1e-5f, s.cin, s.cout, s.kind, p + im.w, p + im.scale,
+                               p + im.shift, st);
         }
-        p += layer_floats(s);
+        if (im.t2pair >= 0) launch_conv3d_t2_pair_pack(p + im.w, p + im.t2pair, st);      // from the image just packed
+        if (im.pk8 >= 0) launch_conv3d_pk8_pack(w, wd, s.cin, p + im.pk8, st);
+        if (im.b4 >= 0) launch_conv3d_b4_pack(w, wd, s.cin, p + im.b4, st);
+        p += im.floats;
     }
     return check_launch("cost_reg_pack");
 }
 size_t enerf_cost_reg_workspace_bytes(int full, int B, int D, int h, int w) {
-    long long n0 = (long long)B * D * h * w, n1 = n0 / 8, n2 = n1 / 8, n3 = n2 / 8;
-    long long f = n0 * 8 /*c0*/ + n1 * 16 * 2 /*c1,c2*/ + n2 * 32 * 2 /*c3,c4*/ + n1 * 16 /*y9*/ + n0 * 8 /*y11*/;
-    if (full) f += n3 * 64 * 2 + n2 * 32;
+    long long floats[kNumBufs], f = 0;
+    const int n = costreg_buffers(full, (long long)B * D * h * w, floats);
+    for (int i = 0; i < n; ++i) f += floats[i];
     return (size_t)f * sizeof(float);
 }
 int enerf_cost_reg(const float* packed, int in_channels, int full, const float* vol, int B, int D, int h, int w,
@@ -226,69 +250,66 @@ int enerf_cost_reg(const float* packed, int in_channels, int full, const float* 
 }
 }  // extern "C"
 namespace enerf {
+bool cost_reg_conv0_planar(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w) {
+    return cost_reg_plan(in_channels, full, B, D, h, w, o, device_cu_count()).vol_planar_ok;
+}
 int cost_reg_run(const float* packed, int in_channels, int full, const float* vol, int vol_planar, int B, int D, int h, int w,
                  float* feat, float* prob, void* workspace, size_t workspace_bytes, const enerf_options_t* options,
-                 hipStream_t stream, const CostRegHook* hook) {
+                 hipStream_t st, const CostRegHook* hook) {
     REQUIRE(packed && vol && feat && prob && workspace, "cost_reg: null pointer");
     REQUIRE(in_channels == 8 || in_channels == 16 || in_channels == 32, "cost_reg: in_channels=%d unsupported (8/16/32)",
             in_channels);
     REQUIRE(B > 0 && D > 0 && h > 0 && w > 0, "cost_reg: bad shape");
-    const Options opt = resolve_options(options);
     int div = full ? 8 : 4;
     REQUIRE(D % div == 0 && h % div == 0 && w % div == 0, "cost_reg: D,h,w (%d,%d,%d) must be divisible by %d", D, h, w, div);
     if (workspace_bytes < enerf_cost_reg_workspace_bytes(full, B, D, h, w))
         return fail(ENERF_EWORKSPACE, "cost_reg: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    LayerSpec L[12];
-    int n = costreg_layers(in_channels, full, L);
-    Conv3dDesc desc[12];
-    const float* p = packed;
-    for (int i = 0; i < n; ++i) {
-        long long wf = conv3d_packed_floats(L[i].cin, L[i].cout, L[i].kind);
-        int cp = cdiv(L[i].cout, 16) * 16;
-        desc[i] = {p, p + wf, p + wf + cp, L[i].cin, L[i].cout, L[i].kind, L[i].relu,
-                   layer_pk8(L[i]) ? p + wf + 2 * cp : nullptr,                           // scale/shift = 1/0 without BN
-                   layer_pk8(L[i]) ? p + wf + 2 * cp + conv3d_pk8_packed_floats(L[i].cin) : nullptr,
-                   layer_t2pair(L[i]) ? p + wf + 2 * cp : nullptr, 0, 0};
-        p += layer_floats(L[i]);
-    }
-    long long n0 = (long long)B * D * h * w, n1 = n0 / 8, n2 = n1 / 8, n3 = n2 / 8;
-    float* ws = (float*)workspace;
-    auto take = [&](long long nf) { float* r = ws; ws += nf; return r; };
-    float *c0 = take(n0 * 8), *c1 = take(n1 * 16), *c2 = take(n1 * 16), *c3 = take(n2 * 32), *c4 = take(n2 * 32);
-    float *y9 = take(n1 * 16), *y11 = take(n0 * 8);
-    // layouts between producer/consumer pairs that are BOTH on the asynchronous kernels: the cost volume (warp -> conv0) and
-    // conv11's output (-> fused heads) travel as channel-quad planes (conv3d_b4.hip k_conv3d_s1_b4g)
-    if (vol_planar && !conv3d_routes_b4_glds(opt, n0, D))
+    const CostRegPlan P = cost_reg_plan(in_channels, full, B, D, h, w, resolve_options(options), device_cu_count());
+    if (vol_planar && !P.vol_planar_ok)
         return fail(ENERF_EINVAL, "cost_reg: a quad-planar volume needs the asynchronously staged conv0 kernel (conv3d_b4 0/2, D % 4 == 0, >= conv3d_lds_min_voxels)");
-    desc[0].in_planar = vol_planar;
-    if (conv3d_routes_b4_glds(opt, n0, D) && conv3d_routes_t2_pair(opt, n1)) desc[n - 2].out_planar = desc[n - 1].in_planar = 1;
-    int i = 0;
+    float* buf[kNumBufs] = {};
+    long long floats[kNumBufs];
+    const int nbuf = costreg_buffers(full, (long long)B * D * h * w, floats);
+    float* ws = (float*)workspace;
+    for (int i = 0; i < nbuf; ++i) { buf[i] = ws; ws += floats[i]; }
     bool ok = true;
-    auto hooked = [&](int layer) { if (hook != nullptr && hook->after_layer == layer) hook->fn(hook->ctx); };
-    ok &= launch_conv3d(desc[i++], vol, nullptr, c0, nullptr, B, D, h, w, opt, st);                    // conv0
-    hooked(0);
-    ok &= launch_conv3d(desc[i++], c0, nullptr, c1, nullptr, B, D, h, w, opt, st);                     // conv1 (s2)
-    hooked(1);
-    ok &= launch_conv3d(desc[i++], c1, nullptr, c2, nullptr, B, D / 2, h / 2, w / 2, opt, st);         // conv2
-    hooked(2);
-    ok &= launch_conv3d(desc[i++], c2, nullptr, c3, nullptr, B, D / 2, h / 2, w / 2, opt, st);         // conv3 (s2)
-    ok &= launch_conv3d(desc[i++], c3, nullptr, c4, nullptr, B, D / 4, h / 4, w / 4, opt, st);         // conv4
-    const float* x = c4;
-    if (full) {
-        float *c5 = take(n3 * 64), *c6 = take(n3 * 64), *y7 = take(n2 * 32);
-        ok &= launch_conv3d(desc[i++], c4, nullptr, c5, nullptr, B, D / 4, h / 4, w / 4, opt, st);     // conv5 (s2)
-        ok &= launch_conv3d(desc[i++], c5, nullptr, c6, nullptr, B, D / 8, h / 8, w / 8, opt, st);     // conv6
-        ok &= launch_conv3d(desc[i++], c6, c4, y7, nullptr, B, D / 8, h / 8, w / 8, opt, st);          // conv4 + conv7
-        x = y7;
+    const float* p = packed;
+    for (int i = 0; i < P.n; ++i) {
+        const LayerSpec& s = P.spec[i];
+        const Conv3dImage im = layer_image(s);
+        Conv3dDesc d = conv3d_desc(p, im, s.cin, s.cout, s.kind, s.relu);
+        p += im.floats;
+        d.in_planar = i == 0 ? vol_planar : (i == P.n - 1 && P.heads_planar);
+        d.out_planar = i == P.n - 2 && P.heads_planar;
+        const bool last = s.out == kFeatProb;
+        ok &= launch_conv3d(d, P.route[i], s.in == kVol ? vol : buf[s.in], s.res == kNoBuf ? nullptr : buf[s.res], last ? feat : buf[s.out],
+                            last ? prob : nullptr, B, D / s.div, h / s.div, w / s.div, st);
+        if (hook != nullptr && hook->after_layer == s.idx) hook->fn(hook->ctx);      // (conv0 .. conv2: the table's first three rows)
     }
-    ok &= launch_conv3d(desc[i++], x, c2, y9, nullptr, B, D / 4, h / 4, w / 4, opt, st);               // conv2 + conv9
-    ok &= launch_conv3d(desc[i++], y9, c0, y11, nullptr, B, D / 2, h / 2, w / 2, opt, st);             // conv0 + conv11
-    ok &= launch_conv3d(desc[i++], y11, nullptr, feat, prob, B, D, h, w, opt, st);                     // feat_conv ++ depth_conv
     if (!ok) return fail(ENERF_EINVAL, "cost_reg: a layer shape has no kernel (in_channels=%d full=%d)", in_channels, full);
     return check_launch("cost_reg");
 }
 }  // namespace enerf
+#ifdef ENERF_EMU
+// emulator build only (tests/test_conv3d_routes.py): the plan of a whole cost-reg network as text, one "name<template values>" per
+// layer in launch order, then "vol_planar=0|1" and "heads_planar=0|1", newline-separated; launches nothing.  Returns the length
+// (a caller with a smaller buffer asks again).
+extern "C" long long emu_cost_reg_routes(int in_channels, int full, int B, int D, int h, int w, const enerf_options_t* options,
+                                         int cu_count, char* buf, long long cap) {
+    const CostRegPlan P = cost_reg_plan(in_channels, full, B, D, h, w, resolve_options(options), cu_count);
+    std::string t;
+    char name[64];
+    for (int i = 0; i < P.n; ++i) {
+        conv3d_route_name(P.route[i], name, sizeof(name));
+        t += name;
+        t += "\n";
+    }
+    t += P.vol_planar_ok ? "vol_planar=1\n" : "vol_planar=0\n";
+    t += P.heads_planar ? "heads_planar=1\n" : "heads_planar=0\n";
+    if (buf != nullptr && cap > 0) memcpy(buf, t.data(), t.size() < (size_t)cap ? t.size() : (size_t)cap);
+    return (long long)t.size();
+}
+#endif
 extern "C" {
 
 int enerf_depth_regression(const float* prob, const float* depth_values, int B, int D, int h, int w, int depth_inv,

@@ -391,49 +391,6 @@ static void launch_one(const Conv3dDesc& L, const float* in, const float* residu
                  L.relu, B, Di, Hi, Wi, Do, Ho, Wo, rt_total);
 }
 
-// Pick (row tiles per wave, column tiles per wave): favour operand reuse when the layer has plenty of
-// voxel tiles, favour wave count when it does not (the deep levels have 80..2000 tiles for 1024 SIMDs).
-template <int CIN, int KIND>
-static bool dispatch_rt(const Conv3dDesc& L, const float* in, const float* residual, float* out, float* out2, int B,
-                        int Di, int Hi, int Wi, int small_variant, hipStream_t st) {
-    const int rt_total = cdiv(L.cout, 16);
-    long long n = (KIND == kConvS1) ? (long long)B * Di * Hi * Wi
-                  : (KIND == kConvS2) ? (long long)B * ((Di - 1) / 2 + 1) * ((Hi - 1) / 2 + 1) * ((Wi - 1) / 2 + 1)
-                                      : 8LL * B * Di * Hi * Wi;
-    const long long tiles = cdivl(n, 16);
-    const int ct_default = rt_total == 1 ? 4 : (rt_total == 2 ? 2 : 1);
-    const bool small = cdivl(tiles, ct_default) < 1024;      // fewer waves than SIMDs: split finer
-    if (small && KIND != kConvT2 && CIN >= 16 && (small_variant == 2 || small_variant == 3)) {
-        // A/B (enerf_options_t.conv3d_small_variant): operand reuse instead of wave count for the deep layers
-        if (small_variant == 2 && rt_total >= 2) { launch_one<CIN, 2, KIND, 2>(L, in, residual, out, out2, B, Di, Hi, Wi, st); return true; }
-        launch_one<CIN, 1, KIND, 4>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
-        return true;
-    }
-    if (small) {
-        // taps split by kd over three waves + LDS reduction (a 9-way split and no split both measured slower)
-        if (KIND != kConvT2 && CIN >= 16) launch_one<CIN, 1, KIND, 1, (KIND != kConvT2 && CIN >= 16 ? 3 : 1)>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
-        else launch_one<CIN, 1, KIND, 1>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
-        return true;
-    }
-    switch (rt_total) {
-        case 1: launch_one<CIN, 1, KIND, 4>(L, in, residual, out, out2, B, Di, Hi, Wi, st); return true;
-        case 2: launch_one<CIN, 2, KIND, 2>(L, in, residual, out, out2, B, Di, Hi, Wi, st); return true;
-        case 4: launch_one<CIN, 4, KIND, 1>(L, in, residual, out, out2, B, Di, Hi, Wi, st); return true;
-        default: return false;
-    }
-}
-template <int KIND>
-static bool dispatch_cin(const Conv3dDesc& L, const float* in, const float* residual, float* out, float* out2, int B,
-                         int Di, int Hi, int Wi, int sv, hipStream_t st) {
-    switch (L.cin) {
-        case 8: return dispatch_rt<8, KIND>(L, in, residual, out, out2, B, Di, Hi, Wi, sv, st);
-        case 16: return dispatch_rt<16, KIND>(L, in, residual, out, out2, B, Di, Hi, Wi, sv, st);
-        case 32: return dispatch_rt<32, KIND>(L, in, residual, out, out2, B, Di, Hi, Wi, sv, st);
-        case 64: return dispatch_rt<64, KIND>(L, in, residual, out, out2, B, Di, Hi, Wi, sv, st);
-        default: return false;
-    }
-}
-
 // =====================================================================================================
 // V2: stride-1 convolution with the haloed input box staged in LDS.
 // A block (4 waves) owns a BD x 8 x 16 box of output voxels = BD*8 MFMA column tiles (16 consecutive x
@@ -610,96 +567,275 @@ static void launch_s1_lds(const Conv3dDesc& L, const float* in, float* out, floa
     ENERF_LAUNCH((k_conv3d_s1_lds<CIN, RT, BD, BH>), grid, 256, shmem, st, L.w, L.scale, L.shift, in, out, out2, L.cout,
                  L.relu, B, D, H, W, nbd, nbh, nbw);
 }
-template <int CIN>
-static bool dispatch_s1_lds(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W,
-                            hipStream_t st) {
-    const int rt_total = cdiv(L.cout, 16);
-    if (rt_total == 1) {
-        // box depth 4 (2 blocks/CU, fewer halo reads) for layers that fill the chip, depth 2 for the mid-size ones
-        // (level-1 conv2: 160 boxes of depth 4 leave 96 CUs idle).
-        const long long boxes4 = (long long)B * cdiv(D, 4) * cdiv(H, 8) * cdiv(W, 16);
-        const int bd = boxes4 >= 256 ? 4 : 2;   // measured: L0 conv2 20 -> 12.5 us; 480-box layers stay at 4
-        const int bh = boxes4 >= 256 ? 8 : 4;   // mid-size layers: 2 x 4 x 16 boxes, 4x the blocks
-        if (D % 4 == 0 && bd == 4) launch_s1_lds<CIN, 1, 4>(L, in, out, out2, B, D, H, W, st);
-        else if (bh == 4) launch_s1_lds<CIN, 1, 2, 4>(L, in, out, out2, B, D, H, W, st);
-        else launch_s1_lds<CIN, 1, 2>(L, in, out, out2, B, D, H, W, st);
-        return true;
-    }
-    if (rt_total == 2) { launch_s1_lds<CIN, 2, 2>(L, in, out, out2, B, D, H, W, st); return true; }
-    return false;
+// =====================================================================================================
+// Kernel selection: conv3d_route decides, launch_conv3d launches what it decided.
+// =====================================================================================================
+#ifndef ENERF_B4_CB
+#define ENERF_B4_CB 1                // b4c against b4g: 1 = by slot-rounds (route_b4), 2 = b4c always, 0 = never
+#endif
+#ifndef ENERF_WL_MIN_BLOCKS
+#define ENERF_WL_MIN_BLOCKS 400      // measured (level-1 conv4, 640 column tiles x 2 row tiles): 2 tiles per block 14.3 us, 4: 17.6, 1: 16
+#endif
+
+namespace {
+struct Geo {                         // what every rule below reads: the layer, its operands, its input volume, the caller's choices
+    const Conv3dLayer& L;
+    bool residual, out2;
+    int B, Di, Hi, Wi;
+    const Options& o;
+    int cus;
+    bool lds_ok;                     // !conv3d_global_only
+    long long min_vox, vox_in, n_out;      // conv3d_lds_min_voxels resolved; input voxels; output voxels
+    int rt_total;
+};
+Conv3dRoute base(const Geo& g, int family) {
+    Conv3dRoute r;
+    r.family = family; r.cin = g.L.cin; r.cout = g.L.cout; r.kind = g.L.kind;
+    return r;
 }
-// Kernel selection.  `o` carries the caller's explicit choices (enerf_options_t; nothing is read from the environment).
-// Returns false for a layer shape no kernel handles (the C entry reports ENERF_EINVAL).
-bool launch_conv3d(const Conv3dDesc& L, const float* in, const float* residual, float* out, float* out2, int B, int Di,
-                   int Hi, int Wi, const Options& o, hipStream_t st) {
-    const bool lds_ok = !o.conv3d_global_only;
-    const long long min_vox = o.conv3d_lds_min_voxels > 0 ? o.conv3d_lds_min_voxels : 16384;
+
+// every-class transposed kernels (conv3d_t2.hip): conv11 (16 -> 8, x-parity-paired MFMA rows) and conv9 (32 -> 16)
+Conv3dRoute route_t2_all(const Geo& g) {
+    const Conv3dLayer& L = g.L;
+    if (L.kind != kConvT2 || g.out2 || !g.lds_ok || g.o.conv3d_t2_variant == 1) return {};
+    // measured (profiles/r03_conv3d_layers.txt): conv11 16.3 vs 24.0 us (level 1), 10.3 vs 15.2 (level 0); conv9 10.7 vs
+    // 17.2 (level 1) but 10.1 vs 9.1 at level 0's 3840 positions (240 q-tiles: too few blocks)
+    const bool big = L.cout == 8 ? g.vox_in >= g.min_vox : g.vox_in >= g.min_vox / 2;
+    if (!big && g.o.conv3d_t2_variant < 2) return {};
+    if (g.n_out * L.cout >= (1LL << 32)) return {};                                  // 32-bit output offsets
+    if (!((L.cin == 16 && L.cout == 8 && L.t2pair) || (L.cin == 32 && L.cout == 16))) return {};
+    // q-boxes (measured, tools/bench_conv3d_layers.py): conv11 1 x 4 x 16 (15.8 / 9.7 us at level 1 / 0; 2 x 4 x 16: 16.5 / 10.5;
+    // 2 x 8 x 16: 21.0 / 12.5), conv9 1 x 4 x 16 (10.9 us; 1 x 8 x 16: 15.9)
+    Conv3dRoute r = base(g, kRouteT2All);
+    r.bd = 1; r.bh = 4;
+    return r;
+}
+// round-2 LDS-staged transposed path (conv11, 16 -> 8, one class per MFMA): kept for A/B (conv3d_t2_variant = 1)
+Conv3dRoute route_t2_lds(const Geo& g) {
+    if (g.L.kind != kConvT2 || g.out2 || !g.lds_ok || 8 * g.vox_in < 32 * g.min_vox || g.L.cin != 16 || g.L.cout != 8) return {};
+    return base(g, kRouteT2Lds);
+}
+// LDS-staged stride-2 path (conv1 of both nets).  Level-1 conv1: 19.7 -> 14.1 us; level 0 is no faster
+Conv3dRoute route_s2_lds(const Geo& g) {
+    if (g.L.kind != kConvS2 || g.residual || g.out2 || !g.lds_ok || g.vox_in < 32 * g.min_vox || g.L.cin != 8 || g.L.cout > 16) return {};
+    return base(g, kRouteS2Lds);
+}
+// where the kernels written for the stride-1 Cout = 8 layers (conv0 of both levels) and the fused 8 + 1 heads may run
+bool cout8_site(const Geo& g) { return g.L.kind == kConvS1 && !g.residual && g.lds_ok && g.vox_in >= g.min_vox; }
+// batched-4x4 path: no wasted MFMA rows.  conv3d_b4: 0 / 2 = the asynchronously staged kernels where the depth is a multiple of their
+// box, 3 = the register-staged round-2 kernel only, 1 = off
+Conv3dRoute route_b4(const Geo& g) {
+    const bool heads = g.L.cout == 9 && g.out2;
+    if (g.o.conv3d_b4 == 1 || !g.L.b4 || !cout8_site(g) || !((g.L.cout == 8 && !g.out2) || heads)) return {};
+    if (heads ? g.L.cin != 8 : (g.L.cin != 8 && g.L.cin != 16 && g.L.cin != 32)) return {};    // the fused heads of both nets have Cin = 8
+    Conv3dRoute r = base(g, kRouteB4);
+    r.heads = heads;
+    r.bd = g.Di % 4 == 0 ? 4 : 2; r.bh = 8;
+    if (g.o.conv3d_b4 == 3 || r.bd != 4) return r;
+    // b4g or b4c.  Measured (profiles/r05_ab_b4c_conv3d_upfront.txt): 34.8 KB of LDS per block lets FOUR b4c blocks share a CU where b4g has
+    // three.  What decides is the occupancy QUANTISATION, not the box count — with k co-resident blocks per CU a layer of n boxes needs
+    // ceil(n / (CUs k)) rounds of k slots: zju level 0 (1024 boxes = exactly one round of four: 79.4 -> 65.3 us) and zju level 1 (4096 =
+    // four rounds of four instead of 5.33 of three) want b4c, dtu level 1 (1280 = 3 + 2 instead of 4 + 1: 46.1 -> 51.4 us) wants b4g; the
+    // heads / dtu level 0 (1920 boxes) are unchanged: the tap loops were already at the instruction's rate.  b4c is taken when its
+    // slot-rounds ceil(n / (4 CUs)) * 4 do not exceed b4g's ceil(n / (3 CUs)) * 3.
+    // (half-depth boxes — 2 x 8 x 16 on the register-weight kernel, five co-resident blocks per CU — measured in round 5 and not kept:
+    // tools/patches/r06_pruned_knobs.diff)
+    const long long boxes = (unsigned)((long long)g.B * cdiv(g.Di, 4) * cdiv(g.Hi, 8) * cdiv(g.Wi, 16));    // = the launch's grid
+    const long long sr4 = cdivl(boxes, 4LL * g.cus) * 4, sr3 = cdivl(boxes, 3LL * g.cus) * 3;
+    r.family = (ENERF_B4_CB == 2 || (ENERF_B4_CB == 1 && sr4 <= sr3)) ? kRouteB4c : kRouteB4g;
+    return r;
+}
+// tap-packed path: 2/3 of the MFMAs.  Measured on MI355X (same box, rocprofv3): Cin=16 conv0 80-88 us vs 94 us for the plain LDS
+// kernel; Cin=32 conv0 and the Cin=8 heads are no faster (fewer MFMAs, but 14/16 column efficiency, 15 % more blocks and a heavier
+// epilogue eat the gain), so by default only Cin=16 takes this path; conv3d_pk8 == 2 routes every Cout=8(+1) layer here, 1 none.
+// Re-measured after the VALU work: the Cin=8 fused heads gain at level 1 only (655,360 voxels: 54.3 -> 50.6 us; level 0:
+// 20.9 -> 24.2 us), so they take this path above 512 K voxels.
+Conv3dRoute route_pk8(const Geo& g) {
+    if (g.o.conv3d_pk8 == 1 || !g.L.pk8 || !cout8_site(g) || !(g.L.cout == 8 || (g.L.cout == 9 && g.out2))) return {};
+    if (g.o.conv3d_pk8 != 2 && !(g.L.cin == 16 || (g.L.cin == 8 && g.vox_in >= (1LL << 19)))) return {};
+    if (g.L.cin != 8 && g.L.cin != 16 && g.L.cin != 32) return {};
+    Conv3dRoute r = base(g, kRoutePk8);
+    r.bd = g.Di % 4 == 0 ? 4 : 2; r.bh = 8;
+    return r;
+}
+// LDS-staged path: stride-1 layers with enough voxels to fill the chip and cout <= 32
+Conv3dRoute route_s1_lds(const Geo& g) {
+    const Conv3dLayer& L = g.L;
+    if (L.kind != kConvS1 || g.residual || !g.lds_ok || L.cout > 32 || g.vox_in < g.min_vox) return {};
+    if (L.cin != 8 && L.cin != 16 && L.cin != 32) return {};
+    Conv3dRoute r = base(g, kRouteS1Lds);
+    r.rt = g.rt_total; r.bd = 2; r.bh = 8;
+    if (g.rt_total == 1) {
+        // box depth 4 (2 blocks/CU, fewer halo reads) for layers that fill the chip, 2 x 4 x 16 boxes (4x the blocks) for the mid-size
+        // ones (level-1 conv2: 160 boxes of depth 4 leave 96 CUs idle; measured: L0 conv2 20 -> 12.5 us; 480-box layers stay at 4)
+        const bool fills = (long long)g.B * cdiv(g.Di, 4) * cdiv(g.Hi, 8) * cdiv(g.Wi, 16) >= 256;
+        if (fills && g.Di % 4 == 0) r.bd = 4;
+        else if (!fills) r.bh = 4;
+    }
+    return r;
+}
+// k_conv3d's (row tiles per wave, column tiles per wave, kd split): favour operand reuse when the layer has plenty of voxel tiles,
+// favour wave count when it does not (the deep levels have 80..2000 tiles for 1024 SIMDs).  *small: fewer waves than SIMDs.
+Conv3dRoute route_global(const Geo& g, bool* small) {
+    const Conv3dLayer& L = g.L;
+    *small = false;
+    if (L.kind < kConvS1 || L.kind > kConvT2 || (L.cin != 8 && L.cin != 16 && L.cin != 32 && L.cin != 64)) return {};
+    const long long tiles = cdivl(g.n_out, 16);
+    const int ct_default = g.rt_total == 1 ? 4 : (g.rt_total == 2 ? 2 : 1);
+    *small = cdivl(tiles, ct_default) < 1024;
+    const bool deep = L.kind != kConvT2 && L.cin >= 16;
+    const int sv = g.o.conv3d_small_variant;
+    Conv3dRoute r = base(g, kRouteGlobal);
+    r.split = 1;
+    if (*small && deep && (sv == 2 || sv == 3)) {
+        // A/B (enerf_options_t.conv3d_small_variant): operand reuse instead of wave count for the deep layers
+        if (sv == 2 && g.rt_total >= 2) { r.rt = 2; r.ct = 2; } else { r.rt = 1; r.ct = 4; }
+    } else if (*small) {
+        // taps split by kd over three waves + LDS reduction (a 9-way split and no split both measured slower)
+        r.rt = 1; r.ct = 1; r.split = deep ? 3 : 1;
+    } else if (g.rt_total == 1 || g.rt_total == 2 || g.rt_total == 4) {
+        r.rt = g.rt_total; r.ct = ct_default;
+    } else {
+        return {};
+    }
+    return r;
+}
+// small deep stride-1 / stride-2 layers whose input is one or two planes thick (level 1's conv4 .. conv6 at 8 depth planes): whole kd
+// taps are padding there, and conv3d_wl.hip skips them per block — copy, loads and MFMAs (conv6 12.0 -> 7.5 us, conv5 8.3 -> 7.3,
+// conv4 15.1 -> 14.3; on thicker volumes the tap-split kernel is as fast or faster: profiles/r06_ab_conv3d_wl.txt).
+// conv3d_small_variant: 0 = this routing, 4 = conv3d_wl for every small layer (A/B), 1 .. 3 = the round-2 .. 5 forms only.
+// `r` is the layer's k_conv3d route, which stays in the result as launch_conv3d's fallback.
+Conv3dRoute route_wl(const Geo& g, Conv3dRoute r, bool small) {
+    const Conv3dLayer& L = g.L;
+    const int sv = g.o.conv3d_small_variant;
+    if (r.family != kRouteGlobal || !small || L.kind == kConvT2 || g.residual || g.out2 || !g.lds_ok || L.cin < 16 || L.cout % 16 != 0 ||
+        !(sv == 4 || (sv == 0 && g.Di <= 2)))
+        return {};
+    if (g.vox_in * L.cin >= (1LL << 31)) return {};                                  // 32-bit voxel arithmetic
+    // the kd taps some output plane reads inside the volume (a contiguous range; all three unless the volume is 1 - 2 planes thick)
+    const int S = L.kind == kConvS2 ? 2 : 1, Do = S == 2 ? (g.Di - 1) / 2 + 1 : g.Di;
+    int kdlo = 3, kdhi = -1;
+    for (int kd = 0; kd < 3; ++kd)
+        for (int d = 0; d < Do; ++d)
+            if (S * d + kd - 1 >= 0 && S * d + kd - 1 < g.Di) { kdlo = kd < kdlo ? kd : kdlo; kdhi = kd > kdhi ? kd : kdhi; break; }
+    if (kdhi < kdlo) return {};
+    // the largest block (most sharing of the weight tile) that still leaves ENERF_WL_MIN_BLOCKS blocks
+    const long long tiles = cdivl(g.n_out, 16);
+    int ctb = 1;
+    for (int c = L.cin == 64 ? 2 : 4; c > 1; c >>= 1)      // Cin = 64: 144 B-operand registers, 12 waves would spill
+        if (cdivl(tiles, c) * g.rt_total >= ENERF_WL_MIN_BLOCKS) { ctb = c; break; }
+    r.family = kRouteWl;
+    r.ctb = ctb; r.kdlo = kdlo; r.nkd = kdhi - kdlo + 1;
+    return r;
+}
+}  // namespace
+
+// `o` carries the caller's explicit choices (enerf_options_t; nothing is read from the environment).  The first rule that takes the
+// layer wins, in this order; kRouteNone (the C entry reports ENERF_EINVAL) when none does.
+Conv3dRoute conv3d_route(const Conv3dLayer& L, bool has_residual, bool has_out2, int B, int Di, int Hi, int Wi, const Options& o,
+                         int cu_count) {
     const long long vox_in = (long long)B * Di * Hi * Wi;
-    // every-class transposed kernels (conv3d_t2.hip): conv11 (16 -> 8, x-parity-paired MFMA rows) and conv9 (32 -> 16)
-    if (L.kind == kConvT2 && out2 == nullptr && lds_ok && o.conv3d_t2_variant != 1) {
-        // measured (profiles/r03_conv3d_layers.txt): conv11 16.3 vs 24.0 us (level 1), 10.3 vs 15.2 (level 0); conv9 10.7 vs
-        // 17.2 (level 1) but 10.1 vs 9.1 at level 0's 3840 positions (240 q-tiles: too few blocks)
-        const bool big = L.cout == 8 ? vox_in >= min_vox : vox_in >= min_vox / 2;
-        if ((big || o.conv3d_t2_variant >= 2) && launch_conv3d_t2_all(L, in, residual, out, B, Di, Hi, Wi, st)) return true;
-    }
-    if (L.out_planar) return false;                    // only the kernel above writes channel-quad planes
-    // round-2 LDS-staged transposed path (conv11, 16 -> 8, one class per MFMA): kept for A/B (conv3d_t2_variant = 1)
-    if (L.kind == kConvT2 && out2 == nullptr && lds_ok && 8 * vox_in >= 32 * min_vox &&
-        launch_conv3d_t2_lds(L, in, residual, out, B, Di, Hi, Wi, st))
-        return true;
-    // LDS-staged stride-2 path (conv1 of both nets).  Level-1 conv1: 19.7 -> 14.1 us; level 0 is no faster
-    if (L.kind == kConvS2 && residual == nullptr && out2 == nullptr && lds_ok && vox_in >= 32 * min_vox &&
-        launch_conv3d_s2_lds(L, in, out, B, Di, Hi, Wi, st))
-        return true;
-    // batched-4x4 path for the Cout=8(+1) stride-1 layers (conv0 of both levels, fused heads): no wasted MFMA rows
-    if (o.conv3d_b4 != 1 && residual == nullptr && lds_ok && vox_in >= min_vox && launch_conv3d_b4(L, in, out, out2, B, Di, Hi, Wi, o.conv3d_b4 != 3, st))
-        return true;
-    if (L.in_planar) return false;                     // only the asynchronously staged b4 kernel reads channel-quad planes
-    // tap-packed path for the Cout=8 stride-1 layers (conv0 of both levels, fused heads): 2/3 of the MFMAs
-    if (o.conv3d_pk8 != 1 && residual == nullptr && lds_ok && vox_in >= min_vox &&
-        launch_conv3d_pk8(L, in, out, out2, B, Di, Hi, Wi, o.conv3d_pk8 == 2, st))
-        return true;
-    // LDS-staged path: stride-1 layers with enough voxels to fill the chip and cout <= 32
-    if (L.kind == kConvS1 && residual == nullptr && lds_ok && L.cout <= 32 && vox_in >= min_vox) {
-        bool ok = false;
-        switch (L.cin) {
-            case 8: ok = dispatch_s1_lds<8>(L, in, out, out2, B, Di, Hi, Wi, st); break;
-            case 16: ok = dispatch_s1_lds<16>(L, in, out, out2, B, Di, Hi, Wi, st); break;
-            case 32: ok = dispatch_s1_lds<32>(L, in, out, out2, B, Di, Hi, Wi, st); break;
-            default: break;
-        }
-        if (ok) return true;
-    }
-    // small deep stride-1 / stride-2 layers whose input is one or two planes thick (level 1's conv4 .. conv6 at 8 depth planes): whole kd
-    // taps are padding there, and conv3d_wl.hip skips them per block — copy, loads and MFMAs (conv6 12.0 -> 7.5 us, conv5 8.3 -> 7.3,
-    // conv4 15.1 -> 14.3; on thicker volumes the tap-split kernel below is as fast or faster: profiles/r06_ab_conv3d_wl.txt).
-    // conv3d_small_variant: 0 = this routing, 4 = conv3d_wl for every small layer (A/B), 1 .. 3 = the round-2 .. 5 forms only
-    if ((L.kind == kConvS1 || L.kind == kConvS2) && residual == nullptr && out2 == nullptr && lds_ok && L.cin >= 16 &&
-        L.cout % 16 == 0 && (o.conv3d_small_variant == 4 || (o.conv3d_small_variant == 0 && Di <= 2))) {
-        const int rt_total = cdiv(L.cout, 16), ct_default = rt_total == 1 ? 4 : (rt_total == 2 ? 2 : 1);
-        const long long n = L.kind == kConvS1 ? vox_in : (long long)B * ((Di - 1) / 2 + 1) * ((Hi - 1) / 2 + 1) * ((Wi - 1) / 2 + 1);
-        if (cdivl(cdivl(n, 16), ct_default) < 1024 && launch_conv3d_wl(L, in, out, B, Di, Hi, Wi, st)) return true;
-    }
-    switch (L.kind) {
-        case kConvS1: return dispatch_cin<kConvS1>(L, in, residual, out, out2, B, Di, Hi, Wi, o.conv3d_small_variant, st);
-        case kConvS2: return dispatch_cin<kConvS2>(L, in, residual, out, out2, B, Di, Hi, Wi, o.conv3d_small_variant, st);
-        case kConvT2: return dispatch_cin<kConvT2>(L, in, residual, out, out2, B, Di, Hi, Wi, o.conv3d_small_variant, st);
-        default: return false;
+    const long long n_out = L.kind == kConvS1   ? vox_in
+                            : L.kind == kConvS2 ? (long long)B * ((Di - 1) / 2 + 1) * ((Hi - 1) / 2 + 1) * ((Wi - 1) / 2 + 1)
+                                                : 8 * vox_in;
+    const Geo g = {L, has_residual, has_out2, B, Di, Hi, Wi, o, cu_count, !o.conv3d_global_only,
+                   o.conv3d_lds_min_voxels > 0 ? o.conv3d_lds_min_voxels : 16384, vox_in, n_out, cdiv(L.cout, 16)};
+    Conv3dRoute r;
+    if ((r = route_t2_all(g)).family) return r;
+    if ((r = route_t2_lds(g)).family) return r;
+    if ((r = route_s2_lds(g)).family) return r;
+    if ((r = route_b4(g)).family) return r;
+    if ((r = route_pk8(g)).family) return r;
+    if ((r = route_s1_lds(g)).family) return r;
+    bool small;
+    const Conv3dRoute global = route_global(g, &small);
+    if ((r = route_wl(g, global, small)).family) return r;
+    return global;
+}
+bool conv3d_route_planar_in(const Conv3dRoute& r) { return r.family == kRouteB4g || r.family == kRouteB4c; }
+bool conv3d_route_planar_out(const Conv3dRoute& r) { return r.family == kRouteT2All && r.cout == 8; }
+void conv3d_route_name(const Conv3dRoute& r, char* buf, size_t cap) {
+    const char* tf = r.heads ? "true" : "false";
+    switch (r.family) {
+        case kRouteT2All: snprintf(buf, cap, "t2_all<%d,%d,%d,%d>", r.cin, r.cout, r.bd, r.bh); break;
+        case kRouteT2Lds: snprintf(buf, cap, "t2_lds<%d>", r.cin); break;
+        case kRouteS2Lds: snprintf(buf, cap, "s2_lds<%d>", r.cin); break;
+        case kRouteB4: snprintf(buf, cap, "s1_b4<%d,%d,%s>", r.cin, r.bd, tf); break;
+        case kRouteB4g: snprintf(buf, cap, "s1_b4g<%d,%d,%s>", r.cin, r.bd, tf); break;
+        case kRouteB4c: snprintf(buf, cap, "s1_b4c<%d,%d,%s>", r.cin, r.bd, tf); break;
+        case kRoutePk8: snprintf(buf, cap, "s1_pk8<%d,%d>", r.cin, r.bd); break;
+        case kRouteS1Lds: snprintf(buf, cap, "s1_lds<%d,%d,%d,%d>", r.cin, r.rt, r.bd, r.bh); break;
+        case kRouteWl: snprintf(buf, cap, "wl<%d,%d,%d>", r.cin, r.kind, r.ctb); break;
+        case kRouteGlobal: snprintf(buf, cap, "conv3d<%d,%d,%d,%d,%d>", r.cin, r.rt, r.kind, r.ct, r.split); break;
+        default: snprintf(buf, cap, "none"); break;
     }
 }
 
-// The layout decisions enerf_cost_reg / enerf_forward make BEFORE the launches must mirror the routing above.
-bool conv3d_routes_b4_glds(const Options& o, long long vox, int D) {
-    const long long min_vox = o.conv3d_lds_min_voxels > 0 ? o.conv3d_lds_min_voxels : 16384;
-    return o.conv3d_b4 != 1 && o.conv3d_b4 != 3 && !o.conv3d_global_only && vox >= min_vox && D % 4 == 0;
+template <int CIN>
+static void dispatch_s1_lds(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H,
+                            int W, hipStream_t st) {
+    if (r.rt == 1 && r.bd == 4) launch_s1_lds<CIN, 1, 4>(L, in, out, out2, B, D, H, W, st);
+    else if (r.rt == 1 && r.bh == 4) launch_s1_lds<CIN, 1, 2, 4>(L, in, out, out2, B, D, H, W, st);
+    else if (r.rt == 1) launch_s1_lds<CIN, 1, 2>(L, in, out, out2, B, D, H, W, st);
+    else launch_s1_lds<CIN, 2, 2>(L, in, out, out2, B, D, H, W, st);
 }
-bool conv3d_routes_t2_pair(const Options& o, long long vox_in) {
-    const long long min_vox = o.conv3d_lds_min_voxels > 0 ? o.conv3d_lds_min_voxels : 16384;
-    return !o.conv3d_global_only && o.conv3d_t2_variant != 1 && (vox_in >= min_vox || o.conv3d_t2_variant >= 2);
+static void launch_s1(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
+                      hipStream_t st) {
+    switch (r.cin) {
+        case 8: return dispatch_s1_lds<8>(L, r, in, out, out2, B, D, H, W, st);
+        case 16: return dispatch_s1_lds<16>(L, r, in, out, out2, B, D, H, W, st);
+        default: return dispatch_s1_lds<32>(L, r, in, out, out2, B, D, H, W, st);
+    }
 }
-bool cost_reg_wants_planar_volume(const enerf_options_t& o, int in_channels, int B, int D, int h, int w) {
-    (void)in_channels;
-    return conv3d_routes_b4_glds(o, (long long)B * D * h * w, D);
+template <int CIN, int KIND>
+static void dispatch_rt(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out,
+                        float* out2, int B, int Di, int Hi, int Wi, hipStream_t st) {
+    constexpr int SPLIT = (KIND != kConvT2 && CIN >= 16) ? 3 : 1;      // the only split instantiated, and only for the deep layers
+    if (r.rt == 2) launch_one<CIN, 2, KIND, 2>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
+    else if (r.rt == 1 && r.ct == 4) launch_one<CIN, 1, KIND, 4>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
+    else if (r.split == 3) launch_one<CIN, 1, KIND, 1, SPLIT>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
+    else if (r.rt == 1) launch_one<CIN, 1, KIND, 1>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
+    else launch_one<CIN, 4, KIND, 1>(L, in, residual, out, out2, B, Di, Hi, Wi, st);
+}
+template <int KIND>
+static void dispatch_cin(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out,
+                         float* out2, int B, int Di, int Hi, int Wi, hipStream_t st) {
+    switch (r.cin) {
+        case 8: return dispatch_rt<8, KIND>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+        case 16: return dispatch_rt<16, KIND>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+        case 32: return dispatch_rt<32, KIND>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+        default: return dispatch_rt<64, KIND>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+    }
+}
+static void launch_global(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out,
+                          float* out2, int B, int Di, int Hi, int Wi, hipStream_t st) {
+    switch (r.kind) {
+        case kConvS1: return dispatch_cin<kConvS1>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+        case kConvS2: return dispatch_cin<kConvS2>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+        default: return dispatch_cin<kConvT2>(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+    }
+}
+
+bool launch_conv3d(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out, float* out2, int B,
+                   int Di, int Hi, int Wi, hipStream_t st) {
+    switch (r.family) {
+        case kRouteT2All: launch_conv3d_t2_all(L, r, in, residual, out, B, Di, Hi, Wi, st); return true;
+        case kRouteT2Lds: launch_conv3d_t2_lds(L, in, residual, out, B, Di, Hi, Wi, st); return true;
+        case kRouteS2Lds: launch_conv3d_s2_lds(L, in, out, B, Di, Hi, Wi, st); return true;
+        case kRouteB4:
+        case kRouteB4g:
+        case kRouteB4c: launch_conv3d_b4(L, r, in, out, out2, B, Di, Hi, Wi, st); return true;
+        case kRoutePk8: launch_conv3d_pk8(L, r, in, out, out2, B, Di, Hi, Wi, st); return true;
+        case kRouteS1Lds: launch_s1(L, r, in, out, out2, B, Di, Hi, Wi, st); return true;
+        case kRouteWl:
+            // The one decision left to launch time: conv3d_wl opts in to > 64 KB of dynamic LDS per instantiation, and where the
+            // runtime refuses that, the layer runs on the k_conv3d form its route carries (what the routing did before conv3d_wl).
+            if (launch_conv3d_wl(L, r, in, out, B, Di, Hi, Wi, st)) return true;
+            launch_global(L, r, in, residual, out, out2, B, Di, Hi, Wi, st);
+            return true;
+        case kRouteGlobal: launch_global(L, r, in, residual, out, out2, B, Di, Hi, Wi, st); return true;
+        default: return false;
+    }
 }
 
 }  // namespace enerf

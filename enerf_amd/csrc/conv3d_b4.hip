@@ -512,32 +512,21 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4c(const float* __restric
     }
 }
 
-// Measured (profiles/r05_ab_b4c_conv3d_upfront.txt): 34.8 KB of LDS per block lets FOUR blocks share a CU where b4g has three.  With >= 8 boxes
-// per CU that pays (zju level-0 conv0, 4096 boxes: 79.4 -> 65.3 us; zju level 1: 133.8 -> 131.0); at ~5 boxes per CU the
-// occupancy quantisation loses (dtu level-1 conv0, 1280 boxes = 4 + 1 instead of 3 + 2 per CU: 46.1 -> 51.4 us), and the
-// heads / dtu level 0 (1920 boxes) are unchanged: the tap loops were already at the instruction's rate.
-// Routing (round 5, second pass): what decides is the occupancy QUANTISATION, not the box count — with k co-resident blocks per CU a
-// layer of n boxes needs ceil(n / (CUs k)) rounds of k slots: zju level 0 (1024 boxes = exactly one round of four: 79.4 -> 65.3 us) and
-// zju level 1 (4096 = four rounds of four instead of 5.33 of three) want b4c, dtu level 1 (1280 = 3 + 2 instead of 4 + 1) wants b4g.
-// b4c is taken when its slot-rounds ceil(n / (4 CUs)) * 4 do not exceed b4g's ceil(n / (3 CUs)) * 3.
-#ifndef ENERF_B4_CB
-#define ENERF_B4_CB 1                // 1: route by slot-rounds (above); 2: b4c always; 0: never
-#endif
+// b4g against b4c (four co-resident blocks per CU instead of three) is a routing decision: conv3d.hip route_b4
+template <int CIN, int BD, bool HEADS>
+static void launch_b4c(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W, hipStream_t st) {
+    constexpr int NVOX = (BD + 2) * 10 * 18, NCH = (NVOX + 63) / 64;
+    const int nbd = cdiv(D, BD), nbh = cdiv(H, 8), nbw = cdiv(W, 16);
+    const unsigned grid = (unsigned)((long long)B * nbd * nbh * nbw);
+    const size_t shmem_c = (size_t)2 * (NCH + (HEADS ? 1 : 0)) * 64 * 4 * sizeof(float);
+    ENERF_LAUNCH((k_conv3d_s1_b4c<CIN, BD, HEADS>), grid, 256, shmem_c, st, L.w_b4, L.scale, L.shift, in, out, out2, L.relu, B,
+                 D, H, W, nbd, nbh, nbw, L.in_planar);
+}
 template <int CIN, int BD, bool HEADS>
 static void launch_b4g(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W, hipStream_t st) {
     constexpr int NVOX = (BD + 2) * 10 * 18, NCH = (NVOX + 63) / 64, NS = HEADS ? 3 : 2, NWCH = (27 * NS * 4 + 63) / 64;
     const int nbd = cdiv(D, BD), nbh = cdiv(H, 8), nbw = cdiv(W, 16);
     const unsigned grid = (unsigned)((long long)B * nbd * nbh * nbw);
-    const long long cus_ = device_cu_count();
-    // (half-depth boxes — 2 x 8 x 16 on the register-weight kernel, five co-resident blocks per CU — measured in round 5 and not kept:
-    // tools/patches/r06_pruned_knobs.diff)
-    const long long sr4 = cdivl(grid, 4 * cus_) * 4, sr3 = cdivl(grid, 3 * cus_) * 3;
-    if (ENERF_B4_CB == 2 || (ENERF_B4_CB == 1 && sr4 <= sr3)) {
-        const size_t shmem_c = (size_t)2 * (NCH + (HEADS ? 1 : 0)) * 64 * 4 * sizeof(float);
-        ENERF_LAUNCH((k_conv3d_s1_b4c<CIN, BD, HEADS>), grid, 256, shmem_c, st, L.w_b4, L.scale, L.shift, in, out, out2, L.relu, B,
-                     D, H, W, nbd, nbh, nbw, L.in_planar);
-        return;
-    }
     const size_t shmem = (size_t)2 * (NCH + NWCH) * 64 * 4 * sizeof(float);
     ENERF_LAUNCH((k_conv3d_s1_b4g<CIN, BD, HEADS>), grid, 256, shmem, st, L.w_b4, L.scale, L.shift, in, out, out2, L.relu, B, D,
                  H, W, nbd, nbh, nbw, L.in_planar);
@@ -552,32 +541,22 @@ static void launch_b4(const Conv3dDesc& L, const float* in, float* out, float* o
     ENERF_LAUNCH((k_conv3d_s1_b4<CIN, BD, HEADS>), grid, 256, shmem, st, L.w_b4, L.scale, L.shift, in, out, out2, L.relu, B, D,
                  H, W, nbd, nbh, nbw);
 }
-bool launch_conv3d_b4(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W, bool glds,
+template <int CIN, bool HEADS>
+static void dispatch_b4(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
+                        hipStream_t st) {
+    if (r.family == kRouteB4c) launch_b4c<CIN, 4, HEADS>(L, in, out, out2, B, D, H, W, st);
+    else if (r.family == kRouteB4g) launch_b4g<CIN, 4, HEADS>(L, in, out, out2, B, D, H, W, st);
+    else if (r.bd == 4) launch_b4<CIN, 4, HEADS>(L, in, out, out2, B, D, H, W, st);
+    else launch_b4<CIN, 2, HEADS>(L, in, out, out2, B, D, H, W, st);
+}
+void launch_conv3d_b4(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
                       hipStream_t st) {
-    if (L.w_b4 == nullptr || L.kind != kConvS1) return false;
-    if (L.in_planar && !(glds && D % 4 == 0)) return false;       // only the glds kernel reads quad planes
-    const bool heads = L.cout == 9 && out2 != nullptr;
-    if (!(L.cout == 8 && out2 == nullptr) && !heads) return false;
-    const bool bd4 = D % 4 == 0;
-    if (heads) {                                                   // the fused heads of both nets have Cin = 8
-        if (L.cin != 8) return false;
-        if (glds && bd4) launch_b4g<8, 4, true>(L, in, out, out2, B, D, H, W, st);
-        else if (bd4) launch_b4<8, 4, true>(L, in, out, out2, B, D, H, W, st);
-        else launch_b4<8, 2, true>(L, in, out, out2, B, D, H, W, st);
-        return true;
+    if (r.heads) return dispatch_b4<8, true>(L, r, in, out, out2, B, D, H, W, st);
+    switch (r.cin) {
+        case 8: return dispatch_b4<8, false>(L, r, in, out, out2, B, D, H, W, st);
+        case 16: return dispatch_b4<16, false>(L, r, in, out, out2, B, D, H, W, st);
+        default: return dispatch_b4<32, false>(L, r, in, out, out2, B, D, H, W, st);
     }
-#define ENERF_B4(CINV) \
-    if (glds && bd4) launch_b4g<CINV, 4, false>(L, in, out, out2, B, D, H, W, st); \
-    else if (bd4) launch_b4<CINV, 4, false>(L, in, out, out2, B, D, H, W, st); \
-    else launch_b4<CINV, 2, false>(L, in, out, out2, B, D, H, W, st); \
-    return true;
-    switch (L.cin) {
-        case 8: ENERF_B4(8)
-        case 16: ENERF_B4(16)
-        case 32: ENERF_B4(32)
-        default: return false;
-    }
-#undef ENERF_B4
 }
 
 }  // namespace enerf

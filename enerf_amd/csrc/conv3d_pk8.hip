@@ -192,23 +192,13 @@ static void launch_pk8(const Conv3dDesc& L, const float* in, float* out, float* 
     ENERF_LAUNCH((k_conv3d_s1_pk8<CIN, BD>), grid, 256, shmem, st, L.w_pk8, L.scale, L.shift, in, out, out2, L.relu, B, D, H,
                  W, nbd, nbh, nbw);
 }
-bool launch_conv3d_pk8(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W,
-                       bool all_layers, hipStream_t st) {
-    if (L.w_pk8 == nullptr || L.kind != kConvS1 || !(L.cout == 8 || (L.cout == 9 && out2 != nullptr))) return false;
-    // Measured on MI355X (same box, rocprofv3): Cin=16 conv0 80-88 us vs 94 us for the plain LDS kernel; Cin=32
-    // conv0 and the Cin=8 heads are no faster (fewer MFMAs, but 14/16 column efficiency, 15 % more blocks and a
-    // heavier epilogue eat the gain), so by default only Cin=16 takes this path; `all_layers`
-    // (enerf_options_t.conv3d_pk8 == 2) routes every Cout=8(+1) layer here.
-    // Re-measured after the VALU work: the Cin=8 fused heads gain at level 1 only (655,360 voxels: 54.3 -> 50.6 us; level 0:
-    // 20.9 -> 24.2 us), so they take this path above 512 K voxels.
-    const bool big = (long long)B * D * H * W >= (1LL << 19);
-    if (!all_layers && !(L.cin == 16 || (L.cin == 8 && big))) return false;
-    const bool bd4 = (D % 4 == 0);
-    switch (L.cin) {
-        case 8: bd4 ? launch_pk8<8, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<8, 2>(L, in, out, out2, B, D, H, W, st); return true;
-        case 16: bd4 ? launch_pk8<16, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<16, 2>(L, in, out, out2, B, D, H, W, st); return true;
-        case 32: bd4 ? launch_pk8<32, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<32, 2>(L, in, out, out2, B, D, H, W, st); return true;
-        default: return false;
+void launch_conv3d_pk8(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
+                       hipStream_t st) {
+    const bool bd4 = r.bd == 4;
+    switch (r.cin) {
+        case 8: return bd4 ? launch_pk8<8, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<8, 2>(L, in, out, out2, B, D, H, W, st);
+        case 16: return bd4 ? launch_pk8<16, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<16, 2>(L, in, out, out2, B, D, H, W, st);
+        default: return bd4 ? launch_pk8<32, 4>(L, in, out, out2, B, D, H, W, st) : launch_pk8<32, 2>(L, in, out, out2, B, D, H, W, st);
     }
 }
 

@@ -118,16 +118,14 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s2_lds(const float* __restric
     }
 }
 
-// Cin = 8, Cout <= 16 stride-2 layers.  Returns false if the shape is not handled.
-bool launch_conv3d_s2_lds(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st) {
-    if (L.kind != kConvS2 || L.cin != 8 || L.cout > 16) return false;
+// Cin = 8, Cout <= 16 stride-2 layers.
+void launch_conv3d_s2_lds(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st) {
     const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
     const int nbd = cdiv(Do, 2), nbh = cdiv(Ho, 4), nbw = cdiv(Wo, 16);
     const size_t shmem = (size_t)5 * 9 * 33 * 8 * sizeof(float);
     const unsigned grid = (unsigned)((long long)B * nbd * nbh * nbw);
     ENERF_LAUNCH((k_conv3d_s2_lds<8>), grid, 256, shmem, st, L.w, L.scale, L.shift, in, out, L.cout, L.relu, B, Di, Hi, Wi, Do,
                  Ho, Wo, nbd, nbh, nbw);
-    return true;
 }
 
 }  // namespace enerf

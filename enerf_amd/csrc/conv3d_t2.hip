@@ -359,29 +359,21 @@ static void launch_t2_all(const Conv3dDesc& L, const float* in, const float* res
     ENERF_LAUNCH((k_conv3d_t2_all<CIN, COUT, QD, QH>), grid, 256, shmem, st, COUT == 8 ? L.w_t2pair : L.w, L.scale, L.shift, in,
                  residual, out, L.relu, B, Di, Hi, Wi, nbd, nbh, nbw, L.out_planar);
 }
-// conv11 (16 -> 8, class-paired) and conv9 (32 -> 16) of both nets.  Returns false if the shape is not handled.
-bool launch_conv3d_t2_all(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi,
-                          int Wi, hipStream_t st) {
-    if (L.kind != kConvT2) return false;
-    if (L.out_planar && !(L.cin == 16 && L.cout == 8 && L.w_t2pair != nullptr)) return false;
-    if ((long long)B * 8 * Di * Hi * Wi * L.cout >= (1LL << 32)) return false;                        // 32-bit output offsets
-    // q-boxes (measured, tools/bench_conv3d_layers.py): conv11 1 x 4 x 16 (15.8 / 9.7 us at level 1 / 0; 2 x 4 x 16: 16.5 / 10.5;
-    // 2 x 8 x 16: 21.0 / 12.5), conv9 1 x 4 x 16 (10.9 us; 1 x 8 x 16: 15.9)
-    if (L.cin == 16 && L.cout == 8 && L.w_t2pair != nullptr) { launch_t2_all<16, 8, 1, 4>(L, in, residual, out, B, Di, Hi, Wi, st); return true; }
-    if (L.cin == 32 && L.cout == 16) { launch_t2_all<32, 16, 1, 4>(L, in, residual, out, B, Di, Hi, Wi, st); return true; }
-    return false;
+// conv11 (16 -> 8, class-paired) and conv9 (32 -> 16) of both nets; the q-box is 1 x 4 x 16 for both (conv3d.hip route_t2_all)
+void launch_conv3d_t2_all(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out, int B, int Di,
+                          int Hi, int Wi, hipStream_t st) {
+    if (r.cout == 8) launch_t2_all<16, 8, 1, 4>(L, in, residual, out, B, Di, Hi, Wi, st);
+    else launch_t2_all<32, 16, 1, 4>(L, in, residual, out, B, Di, Hi, Wi, st);
 }
 
-// Cin = 16, Cout = 8 transposed layers.  Returns false if the shape is not handled.
-bool launch_conv3d_t2_lds(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi,
+// Cin = 16, Cout = 8 transposed layers.
+void launch_conv3d_t2_lds(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi,
                           int Wi, hipStream_t st) {
-    if (L.kind != kConvT2 || L.cin != 16 || L.cout != 8) return false;
     const int nbd = cdiv(Di, 2), nbh = cdiv(Hi, 4), nbw = cdiv(Wi, 16);
     const size_t shmem = ((size_t)3 * 5 * 17 * 16 + 27 * 4 * 64) * sizeof(float);
     const unsigned grid = (unsigned)((long long)B * nbd * nbh * nbw);
     ENERF_LAUNCH((k_conv3d_t2_lds<16>), grid, 256, shmem, st, L.w, L.scale, L.shift, in, residual, out, L.cout, L.relu, B, Di,
                  Hi, Wi, nbd, nbh, nbw);
-    return true;
 }
 
 }  // namespace enerf

@@ -175,13 +175,15 @@ __global__ __launch_bounds__(CTB * 192) void k_conv3d_wl(const float* __restrict
     }
 }
 
+// false: the > 64 KB dynamic LDS opt-in was refused, nothing launched
 template <int CIN, int KIND, int CTB>
-static bool launch_wl(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
-                      int kdlo, int nkd, hipStream_t st) {
+static bool launch_wl(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st) {
+    constexpr int S = KIND == kConvS2 ? 2 : 1;
+    const int Do = S == 2 ? (Di - 1) / 2 + 1 : Di, Ho = S == 2 ? (Hi - 1) / 2 + 1 : Hi, Wo = S == 2 ? (Wi - 1) / 2 + 1 : Wi;
     const int rt_total = cdiv(L.cout, 16);
     const long long n = (long long)B * Do * Ho * Wo;
     const long long groups = cdivl(cdivl(n, 16), CTB);
-    const size_t shmem = ((size_t)nkd * 9 * (CIN / 4) * 64 + 2 * CTB * 256) * sizeof(float);
+    const size_t shmem = ((size_t)r.nkd * 9 * (CIN / 4) * 64 + 2 * CTB * 256) * sizeof(float);
 #ifndef ENERF_EMU
     if (shmem > 64 * 1024) {                              // opt in to a large dynamic LDS allocation once per instantiation
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3d_wl<CIN, KIND, CTB>),
@@ -190,57 +192,31 @@ static bool launch_wl(const Conv3dDesc& L, const float* in, float* out, int B, i
     }
 #endif
     ENERF_LAUNCH((k_conv3d_wl<CIN, KIND, CTB>), (unsigned)(groups * rt_total), CTB * 192, shmem, st, L.w, L.scale, L.shift, in, out,
-                 L.cout, L.relu, B, Di, Hi, Wi, Do, Ho, Wo, rt_total, kdlo, nkd);
+                 L.cout, L.relu, B, Di, Hi, Wi, Do, Ho, Wo, rt_total, r.kdlo, r.nkd);
     return true;
 }
 
 template <int CIN, int KIND>
-static bool dispatch_wl(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, int min_blocks, hipStream_t st) {
-    constexpr int S = KIND == kConvS2 ? 2 : 1;
-    const int Do = S == 2 ? (Di - 1) / 2 + 1 : Di, Ho = S == 2 ? (Hi - 1) / 2 + 1 : Hi, Wo = S == 2 ? (Wi - 1) / 2 + 1 : Wi;
-    // the kd taps some output plane reads inside the volume (a contiguous range; all three unless the volume is 1 - 2 planes thick)
-    int kdlo = 3, kdhi = -1;
-    for (int kd = 0; kd < 3; ++kd)
-        for (int d = 0; d < Do; ++d)
-            if (S * d + kd - 1 >= 0 && S * d + kd - 1 < Di) { kdlo = kd < kdlo ? kd : kdlo; kdhi = kd > kdhi ? kd : kdhi; break; }
-    if (kdhi < kdlo) return false;
-    const int nkd = kdhi - kdlo + 1;
-    const size_t wbytes = (size_t)nkd * 9 * (CIN / 4) * 256;
-    const int rt_total = cdiv(L.cout, 16);
-    const long long tiles = cdivl((long long)B * Do * Ho * Wo, 16);
-    // the largest block (most sharing of the weight tile) that still leaves min_blocks blocks; the image has to fit beside a second
-    // block's (two blocks per CU) unless the layer has no more blocks than CUs
-    int ctb = 1;
-    for (int c = CIN == 64 ? 2 : 4; c > 1; c >>= 1)      // Cin = 64: 144 B-operand registers, 12 waves would spill
-        if (cdivl(tiles, c) * rt_total >= min_blocks) { ctb = c; break; }
-    (void)wbytes;
+static bool dispatch_wl(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st) {
     if constexpr (CIN != 64)                              // (never instantiated for Cin = 64: that kernel spills 56 registers)
-        if (ctb == 4) return launch_wl<CIN, KIND, 4>(L, in, out, B, Di, Hi, Wi, Do, Ho, Wo, kdlo, nkd, st);
-    switch (ctb) {
-        case 2: return launch_wl<CIN, KIND, 2>(L, in, out, B, Di, Hi, Wi, Do, Ho, Wo, kdlo, nkd, st);
-        default: return launch_wl<CIN, KIND, 1>(L, in, out, B, Di, Hi, Wi, Do, Ho, Wo, kdlo, nkd, st);
+        if (r.ctb == 4) return launch_wl<CIN, KIND, 4>(L, r, in, out, B, Di, Hi, Wi, st);
+    switch (r.ctb) {
+        case 2: return launch_wl<CIN, KIND, 2>(L, r, in, out, B, Di, Hi, Wi, st);
+        default: return launch_wl<CIN, KIND, 1>(L, r, in, out, B, Di, Hi, Wi, st);
     }
 }
 
-#ifndef ENERF_WL_MIN_BLOCKS
-#define ENERF_WL_MIN_BLOCKS 400      // measured (level-1 conv4, 640 column tiles x 2 row tiles): 2 tiles per block 14.3 us, 4: 17.6, 1: 16
-#endif
-
-// Stride-1 / stride-2 layers with Cin in {16, 32, 64} and Cout a multiple of 16, no skip input.  false: not handled, nothing launched.
-bool launch_conv3d_wl(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st) {
-    if (L.kind != kConvS1 && L.kind != kConvS2) return false;
-    if (L.cout % 16 != 0 || L.in_planar || L.out_planar) return false;
-    if ((long long)B * Di * Hi * Wi * L.cin >= (1LL << 31)) return false;               // 32-bit voxel arithmetic
-    const int mb = ENERF_WL_MIN_BLOCKS;
-#define ENERF_WL_CASE(C)                                                                                             \
-    case C:                                                                                                          \
-        return L.kind == kConvS1 ? dispatch_wl<C, kConvS1>(L, in, out, B, Di, Hi, Wi, mb, st)                       \
-                                 : dispatch_wl<C, kConvS2>(L, in, out, B, Di, Hi, Wi, mb, st)
-    switch (L.cin) {
+// Stride-1 / stride-2 layers with Cin in {16, 32, 64} and Cout a multiple of 16, no skip input (conv3d.hip route_wl).
+bool launch_conv3d_wl(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, int B, int Di, int Hi, int Wi,
+                      hipStream_t st) {
+#define ENERF_WL_CASE(C)                                                                                     \
+    case C:                                                                                                  \
+        return r.kind == kConvS1 ? dispatch_wl<C, kConvS1>(L, r, in, out, B, Di, Hi, Wi, st)                \
+                                 : dispatch_wl<C, kConvS2>(L, r, in, out, B, Di, Hi, Wi, st)
+    switch (r.cin) {
         ENERF_WL_CASE(16);
         ENERF_WL_CASE(32);
-        ENERF_WL_CASE(64);
-        default: return false;
+        default: ENERF_WL_CASE(64);
     }
 #undef ENERF_WL_CASE
 }

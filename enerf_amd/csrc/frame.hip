@@ -587,7 +587,7 @@ struct FrameRun {
         const LevelPlan& L = P.L[i];
         float *proj = ws + L.proj, *dv = ws + L.dv, *vol = ws + L.vol;
         need_level(i);                                                     // level i's source maps (side stream for i >= 1)
-        vol_planar = cost_reg_wants_planar_volume(resolve_options(a->options), L.C, a->B, L.D, L.h, L.w) ? 1 : 0;
+        vol_planar = cost_reg_conv0_planar(resolve_options(a->options), L.C, i != 0, a->B, L.D, L.h, L.w) ? 1 : 0;
         int rc;
         if (!vol_planar)
             rc = enerf_build_feature_volume(f[i], proj, dv, a->B, a->S, L.C, L.Hs, L.Ws, L.D, L.h, L.w, vol, st);

@@ -51,10 +51,9 @@ void launch_build_rays(const float* rays8, const float* depth, const float* std,
 // planar = 1: vol as channel-quad planes (B, C/4, D, h, w, 4) instead of channels-last (B, D, h, w, C)
 void launch_feature_volume(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs,
                            int Ws, int D, int h, int w, float* vol, hipStream_t st, int planar = 0);
-// does enerf_cost_reg read a quad-planar volume for this shape under these options? (enerf_forward asks before the warp)
-bool cost_reg_wants_planar_volume(const enerf_options_t& o, int in_channels, int B, int D, int h, int w);
-bool conv3d_routes_b4_glds(const enerf_options_t& o, long long vox, int D);     // mirrors launch_conv3d's routing
-bool conv3d_routes_t2_pair(const enerf_options_t& o, long long vox_in);
+// does conv0 of this cost-reg network read the volume as channel-quad planes? (the frame driver asks before the warp: the answer is
+// conv0's route in the plan cost_reg_run itself launches from, capi.hip cost_reg_plan)
+bool cost_reg_conv0_planar(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w);
 // enerf_cost_reg with the volume layout made explicit (vol_planar = 1: channel-quad planes, see launch_feature_volume)
 // hook: called on the host right after layer `after_layer` (0 = conv0) has been enqueued (enerf_forward uses it to start a
 // side-lane stage at that point of the chain); nullptr = none
@@ -78,24 +77,57 @@ struct Conv3dDesc {
 };
 long long conv3d_t2_pair_floats();
 void launch_conv3d_t2_pair_pack(const float* packed, float* paired, hipStream_t st);   // from the class-major packed image
-// batched 4x4x1 variant for cout = 8 (+ optional depth row on the VALU): see conv3d_b4.hip
-long long conv3d_b4_packed_floats(int cin);
+long long conv3d_b4_packed_floats(int cin);      // batched 4x4x1 image for cout = 8 (+ optional depth row on the VALU): conv3d_b4.hip
 void launch_conv3d_b4_pack(const float* w, const float* wd, int cin, float* packed, hipStream_t st);
-bool launch_conv3d_b4(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W, bool glds,
-                      hipStream_t st);   // glds: the asynchronously staged variant (global_load_lds, two LDS buffers)
-// tap-packed variant for cout = 8 (+ optional depth row): see conv3d_pk8.hip
-long long conv3d_pk8_packed_floats(int cin);
+long long conv3d_pk8_packed_floats(int cin);     // tap-packed image for cout = 8 (+ optional depth row): conv3d_pk8.hip
 void launch_conv3d_pk8_pack(const float* w, const float* wd, int cin, float* packed, hipStream_t st);
-bool launch_conv3d_s2_lds(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi,
-                          hipStream_t st);   // LDS-staged stride-2 variant, Cin = 8, Cout <= 16 (conv3d_s2.hip)
-bool launch_conv3d_t2_lds(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi,
-                          int Wi, hipStream_t st);   // LDS-staged transposed variant, 16 -> 8 (conv3d_t2.hip)
-bool launch_conv3d_t2_all(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi,
-                          int Wi, hipStream_t st);   // every-class transposed kernel: 16 -> 8 (class-paired), 32 -> 16 (conv3d_t2.hip)
-// small deep stride-1 / stride-2 layers (Cin 16 / 32 / 64, Cout % 16 == 0): block-shared weight tile in LDS, operands up front (conv3d_wl.hip)
-bool launch_conv3d_wl(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st);
-bool launch_conv3d_pk8(const Conv3dDesc& L, const float* in, float* out, float* out2, int B, int D, int H, int W,
-                       bool all_layers, hipStream_t st);
+
+// Which kernel a layer runs.  conv3d_route decides it from values alone (no HIP call, no pointer, no static state); the launchers
+// below take the route and only size the grid.  The fields are the template values of the instantiation, named as the kernels name
+// them; conv3d_route_name prints them in the kernel's template order: s1_b4g<16,4,false>, conv3d<32,1,0,1,3>, wl<32,0,2>.
+enum Conv3dFamily {
+    kRouteNone = 0,      // no kernel handles the layer shape
+    kRouteT2All,         // k_conv3d_t2_all<cin, cout, 1, 4>: every-class transposed kernel; cout = 8 is the x-parity-paired form
+    kRouteT2Lds,         // k_conv3d_t2_lds<16>
+    kRouteS2Lds,         // k_conv3d_s2_lds<8>
+    kRouteB4,            // k_conv3d_s1_b4<cin, bd, heads>: register-staged batched 4x4
+    kRouteB4g,           // k_conv3d_s1_b4g<cin, 4, heads>: asynchronously staged (reads channels-last or channel-quad planes)
+    kRouteB4c,           // k_conv3d_s1_b4c<cin, 4, heads>: the same with register-held weights, four blocks per CU
+    kRoutePk8,           // k_conv3d_s1_pk8<cin, bd>
+    kRouteS1Lds,         // k_conv3d_s1_lds<cin, rt, bd, bh>
+    kRouteWl,            // k_conv3d_wl<cin, kind, ctb> over kd taps kdlo .. kdlo + nkd - 1
+    kRouteGlobal         // k_conv3d<cin, rt, kind, ct, split>
+};
+struct Conv3dRoute {
+    int family = kRouteNone;
+    int cin = 0, cout = 0, kind = 0;
+    int bd = 0, bh = 0;                 // output box depth / height of the LDS-staged stride-1 families
+    bool heads = false;                 // b4 families: the fused feat ++ depth heads (depth row on the VALU)
+    int rt = 0, ct = 0, split = 0;      // k_conv3d: row tiles and column tiles per wave, kd split; rt also k_conv3d_s1_lds's
+    int ctb = 0, kdlo = 0, nkd = 0;     // k_conv3d_wl: column tiles per block, the kd taps that fall inside the volume.  (A wl route keeps
+                                        // the layer's k_conv3d values in rt / ct / split: launch_conv3d's one fallback.)
+};
+// what the route needs to know of a layer: its shape and which extra weight images were packed for it
+struct Conv3dLayer { int cin, cout, kind; bool pk8, b4, t2pair; };
+Conv3dRoute conv3d_route(const Conv3dLayer& L, bool has_residual, bool has_out2, int B, int Di, int Hi, int Wi, const Options& o,
+                         int cu_count);
+bool conv3d_route_planar_in(const Conv3dRoute& r);      // the kernel can read channel-quad planes (b4g / b4c)
+bool conv3d_route_planar_out(const Conv3dRoute& r);     // the kernel can write them (the paired t2_all)
+void conv3d_route_name(const Conv3dRoute& r, char* buf, size_t cap);
+
+// The per-file launchers: geometry only, the route has decided.
+void launch_conv3d_b4(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
+                      hipStream_t st);
+void launch_conv3d_pk8(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, float* out2, int B, int D, int H, int W,
+                       hipStream_t st);
+void launch_conv3d_s2_lds(const Conv3dDesc& L, const float* in, float* out, int B, int Di, int Hi, int Wi, hipStream_t st);
+void launch_conv3d_t2_lds(const Conv3dDesc& L, const float* in, const float* residual, float* out, int B, int Di, int Hi, int Wi,
+                          hipStream_t st);
+void launch_conv3d_t2_all(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out, int B, int Di,
+                          int Hi, int Wi, hipStream_t st);
+// false: the runtime refused the > 64 KB dynamic LDS opt-in this instantiation needs; nothing launched (see launch_conv3d)
+bool launch_conv3d_wl(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, float* out, int B, int Di, int Hi, int Wi,
+                      hipStream_t st);
 // number of floats of the packed weight image for a layer
 long long conv3d_packed_floats(int cin, int cout, int kind);
 // pack torch-layout weights (Conv3d: (cout,cin,3,3,3); ConvTranspose3d: (cin,cout,3,3,3)) + BN into
@@ -104,12 +136,37 @@ long long conv3d_packed_floats(int cin, int cout, int kind);
 void launch_conv3d_pack(const float* w, const float* w2, int cout1, const float* bn_w, const float* bn_b, const float* bn_mean, const float* bn_var,
                         float eps, int cin, int cout, int kind, float* packed, float* scale, float* shift,
                         hipStream_t st);
+// One layer's packed image: [weights | scale | shift | pk8 image | b4 image] or [weights | scale | shift | t2-pair image], offsets in
+// floats, -1 = the layer has no such image.  cout8_images: the stride-1 cout = 8 (+ 1) layers of the cost-reg nets (conv0, fused heads).
+struct Conv3dImage { long long w, scale, shift, pk8, b4, t2pair, floats; };
+inline Conv3dImage conv3d_layer_image(int cin, int cout, int kind, bool cout8_images) {
+    Conv3dImage im = {0, conv3d_packed_floats(cin, cout, kind), 0, -1, -1, -1, 0};
+    im.shift = im.scale + cdiv(cout, 16) * 16;
+    im.floats = im.shift + cdiv(cout, 16) * 16;
+    if (cout8_images) {
+        im.pk8 = im.floats;
+        im.b4 = im.pk8 + conv3d_pk8_packed_floats(cin);
+        im.floats = im.b4 + conv3d_b4_packed_floats(cin);
+    }
+    if (kind == kConvT2 && cin == 16 && cout == 8) {        // conv11: x-parity-paired A operands
+        im.t2pair = im.floats;
+        im.floats += conv3d_t2_pair_floats();
+    }
+    return im;
+}
+inline Conv3dLayer conv3d_layer_of(const Conv3dImage& im, int cin, int cout, int kind) {
+    return {cin, cout, kind, im.pk8 >= 0, im.b4 >= 0, im.t2pair >= 0};
+}
+inline Conv3dDesc conv3d_desc(const float* p, const Conv3dImage& im, int cin, int cout, int kind, int relu) {
+    return {p + im.w, p + im.scale, p + im.shift, cin, cout, kind, relu, im.pk8 >= 0 ? p + im.pk8 : nullptr,
+            im.b4 >= 0 ? p + im.b4 : nullptr, im.t2pair >= 0 ? p + im.t2pair : nullptr, 0, 0};
+}
 // in: (B, Di, Hi, Wi, cin) channels-last; out: (B, Do, Ho, Wo, cout_store); residual (same shape as out) optional.
 // cout_store lets the fused heads write feat (8 ch) and prob (1 ch) to two tensors: if out2 != nullptr,
 // channels [0,8) go to out (stride 8) and channel 8 goes to out2 (stride 1).
-// Returns false when no kernel handles the layer shape (nothing launched).
-bool launch_conv3d(const Conv3dDesc& L, const float* in, const float* residual, float* out, float* out2, int B, int Di,
-                   int Hi, int Wi, const Options& o, hipStream_t st);
+// r = conv3d_route(...) of this layer with these operands.  Returns false for kRouteNone (nothing launched).
+bool launch_conv3d(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out, float* out2, int B,
+                   int Di, int Hi, int Wi, hipStream_t st);
 
 // ---- conv2d.hip (FeatureNet) ----------------------------------------------------------------------
 struct Conv2dDesc {
