@@ -492,18 +492,40 @@ class EnerfLib:
         return packed
 
     def render_rays(self, rays12, tex, vol, src_exts, src_ixts, tar_ext, packed, *, n_samples, depth_inv, F,
-                    render_scale, white_bkgd=False, maps=None, options=None):
+                    render_scale, white_bkgd=False, maps=None, options=None, max_blocks=0, ray_index=None, ray_count=None,
+                    scatter_rgb=False, out=None):
         """``rays12`` (B,N,12) from build_rays — or, with ``maps=(depth, std, near_far)`` of the level, the
-        8-float rays (B,N,8): build_rays then runs inside the render kernel."""
+        8-float rays (B,N,8): build_rays then runs inside the render kernel.
+
+        ``max_blocks`` > 0 caps the launch at that many persistent blocks.  ``ray_index`` (int32, device) with ``ray_count``
+        ((1,) int32, device; B must be 1) renders rays ``ray_index[:ray_count]`` only: depth / weights (and rgb, unless
+        ``scatter_rgb``) land compacted in rows ``[0, ray_count)``; with ``scatter_rgb`` rgb goes to row ``ray_index[r]`` (and
+        nowhere when ``ray_count`` <= 1).  Rows the kernel does not write keep what ``out=(rgb, depth, weights)`` held."""
         B, N = rays12.shape[:2]
         if (rays12.shape[-1] != 12) != (maps is not None):
             raise EnerfError("render_rays: pass (B,N,12) rays, or (B,N,8) rays together with maps=(depth,std,near_far)")
+        if (ray_index is None) != (ray_count is None):
+            raise EnerfError("render_rays: pass both ray_index and ray_count or neither")
         S, Hr, Wr = tex.shape[1:4]
         _, D, h, w, _ = vol.shape
         dev = rays12.device
-        rgb = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-        depth = torch.empty((B, N), dtype=torch.float32, device=dev)
-        weights = torch.empty((B, N, n_samples), dtype=torch.float32, device=dev)
+        if out is None:
+            rgb = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+            depth = torch.empty((B, N), dtype=torch.float32, device=dev)
+            weights = torch.empty((B, N, n_samples), dtype=torch.float32, device=dev)
+        else:
+            rgb, depth, weights = out
+            if (tuple(rgb.shape), tuple(depth.shape), tuple(weights.shape)) != ((B, N, 3), (B, N), (B, N, n_samples)):
+                raise EnerfError("render_rays: out=(rgb, depth, weights) must be (B,N,3), (B,N), (B,N,n_samples)")
+            for t in out:
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                    raise EnerfError("render_rays: out=(rgb, depth, weights) must be contiguous float32 on the rays' device")
+        if ray_index is not None:
+            for t in (ray_index, ray_count):
+                if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                    raise EnerfError("render_rays: ray_index / ray_count must be contiguous int32 on the rays' device")
+            if ray_index.numel() < N or ray_count.numel() < 1:
+                raise EnerfError("render_rays: ray_index needs N entries and ray_count one")
         if maps is None:
             fused = (None, None, None, None, 0, 0)
             r12 = _ptr(rays12)
@@ -514,7 +536,9 @@ class EnerfLib:
         a = RenderArgs(r12, _ptr(tex), _ptr(vol), _ptr(src_exts), _ptr(src_ixts), _ptr(tar_ext),
                        _ptr(packed), _ptr(rgb), _ptr(depth), _ptr(weights), B, N, S, n_samples, int(depth_inv), Hr,
                        Wr, F, D, h, w, int(white_bkgd), float(render_scale), *fused,
-                       None if options is None else C.pointer(options))
+                       None if options is None else C.pointer(options),
+                       None if ray_index is None else ray_index.data_ptr(),
+                       None if ray_count is None else ray_count.data_ptr(), int(bool(scatter_rgb)), int(max_blocks))
         self._check(self.dll.enerf_render_rays(C.byref(a), self.stream_of(rays12)), "render_rays")
         return rgb, depth, weights
 

@@ -47,6 +47,16 @@ CASES = {
     # at 1/5 of its size (the reference's U-Nets need H, W divisible by 32): the 2:3 aspect, level-0 volume 32 x 16 x 24
     "llff_small": dict(H=128, W=192, S=3, planes=(32, 8), render_if=(False, True), seed=7, textured=True, human=False,
                        inter="maps", cfg_file="configs/enerf/llff_eval.yaml"),
+    # configs/enerf/dtu_pretrain_nocascade.yaml as shipped (one level: volume_scale 0.25, render_scale 1.0, feature level 2,
+    # nerf_model_feat_ch 8, num_samples 2) with volume_planes 8; its network takes weights_seed0 by the rule "nocascade"
+    # (tests/golden_cases.py::WEIGHT_RULES).  inter: what oracle.forward reports back (no per-sample tensors: size)
+    "nocascade_tiny": dict(H=32, W=64, S=3, planes=(8,), render_if=(True,), seed=8, textured=True, human=False, inter="oracle",
+                           base_cfg="configs/enerf/dtu_pretrain_nocascade.yaml", weights="nocascade"),
+    # configs/enerf/enerf_outdoor/actor1.yaml's enerf block (viewdir_agg False, volume_planes 32,8, num_samples 2,1) on top of its
+    # parent dtu_pretrain.yaml, both levels rendered, through the plain lib.networks.enerf.network: that yaml's network_composite
+    # and its layered foreground are out of scope here
+    "outdoor_tiny": dict(H=32, W=64, S=3, planes=(32, 8), render_if=(True, True), seed=9, textured=True, human=False, inter="oracle",
+                         cas=dict(num_samples=(2, 1)), viewdir_agg=False, weights="outdoor"),
 }
 
 
@@ -87,12 +97,18 @@ def run_case(name: str) -> None:
         assert tuple(cfg.enerf.cas_config.render_if) == c["render_if"]
         assert cfg.network_module.endswith("network_human") == c["human"]
     else:
-        opts = ["enerf.cas_config.volume_planes", ",".join(map(str, c["planes"])),
-                "enerf.cas_config.render_if", ",".join(map(str, c["render_if"]))]
+        lst = lambda v: ",".join(map(str, v)) + ("," if len(v) == 1 else "")       # ("8," parses as a one-element list)
+        opts = ["enerf.cas_config.volume_planes", lst(c["planes"]), "enerf.cas_config.render_if", lst(c["render_if"])]
+        for k, v in c.get("cas", {}).items():
+            opts += [f"enerf.cas_config.{k}", lst(v)]
+        if "viewdir_agg" in c:
+            opts += ["enerf.viewdir_agg", str(c["viewdir_agg"])]
         if c.get("white_bkgd"):
             opts += ["enerf.white_bkgd", "True"]
-        cfg, ref_network = load_reference("configs/enerf/dtu_pretrain.yaml", opts)
+        cfg, ref_network = load_reference(c.get("base_cfg", "configs/enerf/dtu_pretrain.yaml"), opts)
         assert bool(cfg.enerf.white_bkgd) == bool(c.get("white_bkgd"))
+        assert tuple(cfg.enerf.cas_config.volume_planes) == c["planes"] and tuple(cfg.enerf.cas_config.render_if) == c["render_if"]
+        assert bool(cfg.enerf.viewdir_agg) == c.get("viewdir_agg", True) and cfg.network_module == "lib.networks.enerf.network"
     if c["human"]:
         from lib.networks.enerf import network_human as ref_network  # noqa: F811
     from lib.networks.enerf import utils as ref_utils
@@ -100,15 +116,22 @@ def run_case(name: str) -> None:
     torch.manual_seed(0)
     torch.set_num_threads(1)                       # fixed summation order
     net = ref_network.Network().eval()
-    sd = seeded_state_dict(net)
-    net.load_state_dict(sd)
     wpath = os.path.join(GOLDEN, "weights_seed0.npz")
-    wnp = {k: v.numpy() for k, v in sd.items() if not k.endswith("num_batches_tracked")}
-    if os.path.exists(wpath):
-        old = np.load(wpath)
-        assert all(np.array_equal(old[k], wnp[k]) for k in wnp), "weights changed between cases"
+    if c.get("weights"):                           # a network weights_seed0 does not fit as it is: the case's rule derives its state dict
+        from golden_cases import derive_weights
+        wz = np.load(wpath)
+        sd = derive_weights({k: torch.from_numpy(wz[k]) for k in wz.files}, c["weights"])
+        assert set(sd) == {k for k in net.state_dict() if not k.endswith("num_batches_tracked")}
+        net.load_state_dict(sd, strict=False)
     else:
-        np.savez_compressed(wpath, **wnp)
+        sd = seeded_state_dict(net)
+        net.load_state_dict(sd)
+        wnp = {k: v.numpy() for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+        if os.path.exists(wpath):
+            old = np.load(wpath)
+            assert all(np.array_equal(old[k], wnp[k]) for k in wnp), "weights changed between cases"
+        else:
+            np.savez_compressed(wpath, **wnp)
 
     ecfg = EnerfConfig.from_yacs(cfg)
     if c.get("rig") == "lego":
@@ -153,7 +176,7 @@ def run_case(name: str) -> None:
                                            rec.__setitem__(f"feat3d_{level['i']}", a[1])))
     tap("get_img_feat", lambda out, a, k: rec.__setitem__(f"img_{level['i']}", out))
     tap("get_proj_mats", lambda out, a, k: rec.__setitem__(f"proj_{level['i'] + 1}", out))
-    for i in range(2):
+    for i in range(int(cfg.enerf.cas_config.num)):
         m = getattr(net, f"nerf_{i}")
         m.register_forward_hook(lambda mod, inp, out, i=i: rec.__setitem__(f"raw_{i}", out))
         r = getattr(net, f"cost_reg_{i}")
@@ -170,6 +193,10 @@ def run_case(name: str) -> None:
     if inter == "all":
         save.update({f"mid/{k}": v.detach().numpy() for k, v in rec.items()})
         save.update({f"mid/{k}": v.detach().numpy() for k, v in feats.items()})
+    elif inter == "oracle":                        # the stage boundaries oracle.forward(intermediates=) hands back
+        for k, v in rec.items():
+            if k.split("_")[0] in ("vol", "dv", "nf", "feat3d", "prob", "depth", "std", "rays12", "proj"):
+                save[f"mid/{k}"] = v.detach().numpy()
     elif inter == "maps":
         for k, v in rec.items():
             if k.split("_")[0] in ("depth", "std", "nf", "proj", "rays12"):

@@ -11,6 +11,10 @@ from enerf_amd.synth import make_batch, make_lego_batch, make_zju_batch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
+# cas_config of configs/enerf/dtu_pretrain_nocascade.yaml (volume_planes / render_if come from the case)
+NOCASCADE_CAS = dict(num=1, depth_inv=(True,), volume_scale=(0.25,), im_feat_scale=(0.25,), im_ibr_scale=(1.0,), render_scale=(1.0,),
+                     render_im_feat_level=(2,), nerf_model_feat_ch=(8,), num_samples=(2,))
+
 # must mirror oracle/make_golden.py::CASES (the generator is the source of truth)
 CASES = {
     "tiny_s3": dict(H=32, W=64, S=3, planes=(8, 8), render_if=(True, True), seed=1, textured=False, human=False),
@@ -21,12 +25,20 @@ CASES = {
     "zju_small": dict(H=64, W=64, S=4, planes=(32, 8), render_if=(False, True), seed=6, human=True, rig="zju"),
     # configs/enerf/llff_eval.yaml (planes 32,8; 640x960) at 1/5 size (2:3 aspect, level-0 volume 32 x 16 x 24)
     "llff_small": dict(H=128, W=192, S=3, planes=(32, 8), render_if=(False, True), seed=7, textured=True, human=False),
+    # configs/enerf/dtu_pretrain_nocascade.yaml: its one-level cas_config as shipped, volume_planes 8 instead of 48
+    "nocascade_tiny": dict(H=32, W=64, S=3, planes=(8,), render_if=(True,), seed=8, textured=True, human=False,
+                           cas=NOCASCADE_CAS, weights="nocascade"),
+    # configs/enerf/enerf_outdoor/actor1.yaml: viewdir_agg False, num_samples (2, 1), volume_planes (32, 8), both levels rendered
+    # (through the plain network: network_composite and its layered foreground are out of scope)
+    "outdoor_tiny": dict(H=32, W=64, S=3, planes=(32, 8), render_if=(True, True), seed=9, textured=True, human=False,
+                         cas=dict(num_samples=(2, 1)), viewdir_agg=False, weights="outdoor"),
 }
 
 
 def case_config(name: str) -> EnerfConfig:
     c = CASES[name]
-    return EnerfConfig().with_cas(volume_planes=c["planes"], render_if=c["render_if"])
+    cfg = EnerfConfig(viewdir_agg=c.get("viewdir_agg", True))
+    return cfg.with_cas(**c.get("cas", {})).with_cas(volume_planes=c["planes"], render_if=c["render_if"])
 
 
 def case_batch(name: str, as_torch: bool = True) -> dict:
@@ -41,9 +53,34 @@ def case_batch(name: str, as_torch: bool = True) -> dict:
     return {k: torch.from_numpy(v) for k, v in b.items()} if as_torch else b
 
 
-def load_weights() -> dict:
+# The networks of two cases do not take weights_seed0 as it is.  Their state dicts are subsets of it, so instead of storing
+# the same arrays twice more (about 1.5 MB each) a case names how its state dict derives from weights_seed0; the generator
+# asserts that the derived keys are exactly the reference network's (BatchNorm's batch counters aside) before it loads them.
+#   nocascade: one level whose NeRF has 8 feature channels -> that level takes the stored nerf_1 (8 channels); level 1 goes
+#   outdoor:   viewdir_agg False -> Agg has no view_fc
+WEIGHT_RULES = {"nocascade": dict(drop=("nerf_0.", "cost_reg_1."), rename={"nerf_1.": "nerf_0."}),
+                "outdoor": dict(drop=("nerf_0.agg.view_fc.", "nerf_1.agg.view_fc."), rename={})}
+
+
+def derive_weights(sd: dict, rule: str) -> dict:
+    r = WEIGHT_RULES[rule]
+    out = {}
+    for k, v in sd.items():
+        if k.startswith(r["drop"]):
+            continue
+        for a, b in r["rename"].items():
+            if k.startswith(a):
+                k = b + k[len(a):]
+        out[k] = v
+    return out
+
+
+def load_weights(name: str | None = None) -> dict:
+    """The reference state dict of golden case ``name`` (None, or a case of the default networks: weights_seed0)."""
     z = np.load(os.path.join(GOLDEN, "weights_seed0.npz"))
-    return {k: torch.from_numpy(z[k]) for k in z.files}
+    sd = {k: torch.from_numpy(z[k]) for k in z.files}
+    rule = CASES[name].get("weights") if name is not None else None
+    return derive_weights(sd, rule) if rule else sd
 
 
 def load_golden(name: str) -> dict:

@@ -13,9 +13,9 @@ from emu_lib import emu_lib
 from golden_cases import CASES, case_batch, case_config, load_golden, load_weights
 
 
-def _net(cfg, human=False):
+def _net(cfg, human=False, name=None):
     net = (NetworkHuman if human else Network)(cfg, lib=emu_lib()).eval()
-    net.load_state_dict(load_weights(), strict=False)
+    net.load_state_dict(load_weights(name), strict=False)
     return net
 
 
@@ -29,7 +29,7 @@ def _close(a, ref, tol, name=""):
 @pytest.mark.parametrize("name", list(CASES))
 def test_emulated_kernels_match_reference_goldens(name):
     cfg, batch, gold = case_config(name), case_batch(name), load_golden(name)
-    out = _net(cfg, CASES[name]["human"])(batch)
+    out = _net(cfg, CASES[name]["human"], name)(batch)
     assert sorted(out) == sorted(k[4:] for k in gold if k.startswith("out/"))
     for k, v in out.items():
         assert v.shape == gold["out/" + k].shape, k

@@ -11,7 +11,8 @@ import torch
 from enerf_amd.config import EnerfConfig
 from enerf_amd.synth import make_batch
 from oracle import enerf_oracle as O
-from golden_cases import CASES, case_batch, case_config, check_sparse_golden, load_golden, load_weights
+from golden_cases import (CASES, NOCASCADE_CAS, case_batch, case_config, check_sparse_golden, derive_weights, load_golden,
+                          load_weights)
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU (run with -m gpu on the MI355X box)")]
@@ -22,10 +23,10 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _net(cfg, human=False, feature_backend="hip"):
+def _net(cfg, human=False, feature_backend="hip", name=None):
     from enerf_amd.network import Network, NetworkHuman
     net = (NetworkHuman if human else Network)(cfg, feature_backend=feature_backend)   # enerf_amd/libenerf_hip.so
-    net.load_state_dict(load_weights(), strict=False)
+    net.load_state_dict(load_weights(name), strict=False)
     return net.to(_dev()).eval()
 
 
@@ -49,7 +50,7 @@ def test_product_library_is_loaded_not_a_fallback():
 @pytest.mark.parametrize("name", list(CASES))
 def test_goldens(name, backend):
     cfg, gold = case_config(name), load_golden(name)
-    out = _net(cfg, CASES[name]["human"], backend)(_to(case_batch(name)))
+    out = _net(cfg, CASES[name]["human"], backend, name)(_to(case_batch(name)))
     torch.cuda.synchronize()
     assert sorted(out) == sorted(k[4:] for k in gold if k.startswith("out/"))
     for k, v in out.items():
@@ -107,20 +108,40 @@ def test_hip_feature_net_vs_reference_maps():
         assert _rel(a.permute(0, 3, 1, 2).cpu(), g["mid/" + k]) < 1e-5, k
 
 
-@pytest.mark.parametrize("S,B,hw", [(3, 1, (128, 160)), (4, 2, (64, 96)), (2, 1, (96, 128))])
-def test_against_oracle_medium(S, B, hw):
-    """Seeded medium-size frames, both levels rendered, ragged ray lists; oracle on CPU in seconds."""
-    cfg = EnerfConfig().with_cas(volume_planes=(16, 8))
+MEDIUM_VARIANTS = {
+    None: (dict(volume_planes=(16, 8)), True, None),
+    # configs/enerf/dtu_pretrain_nocascade.yaml (one level), 16 planes
+    "nocascade": (dict(NOCASCADE_CAS, volume_planes=(16,), render_if=(True,)), True, "nocascade"),
+    # configs/enerf/enerf_outdoor/actor1.yaml: viewdir_agg False, num_samples (2, 1), planes (32, 8)
+    "outdoor": (dict(volume_planes=(32, 8), num_samples=(2, 1)), False, "outdoor"),
+    # level 1 with 5 samples: the 4-wave render kernel (n_samples 3..8 at 8 feature channels) inside a whole frame
+    "samples35": (dict(volume_planes=(16, 8), num_samples=(3, 5)), True, None)}
+
+
+@pytest.mark.parametrize("S,B,hw,variant", [
+    pytest.param(3, 1, (128, 160), None, id="3-1-hw0"), pytest.param(4, 2, (64, 96), None, id="4-2-hw1"),
+    pytest.param(2, 1, (96, 128), None, id="2-1-hw2"), pytest.param(4, 1, (64, 96), "nocascade", id="nocascade-4-1-64x96"),
+    pytest.param(2, 1, (96, 128), "outdoor", id="outdoor-2-1-96x128"), pytest.param(3, 1, (64, 96), "samples35", id="samples35-3-1-64x96")])
+def test_against_oracle_medium(S, B, hw, variant):
+    """Seeded medium-size frames, every level rendered, ragged ray lists; oracle on CPU in seconds."""
+    cas, vda, rule = MEDIUM_VARIANTS[variant]
+    cfg = EnerfConfig(viewdir_agg=vda).with_cas(**cas)
+    last = cfg.cas.num - 1
     b = make_batch(hw[0], hw[1], S, cfg, seed=100 + S, B=B, textured=True)
     keep = np.random.default_rng(S).permutation(hw[0] * hw[1])[: hw[0] * hw[1] - 37]
-    b["rays_1"] = np.ascontiguousarray(b["rays_1"][:, keep])
+    b[f"rays_{last}"] = np.ascontiguousarray(b[f"rays_{last}"][:, keep])
     batch = {k: torch.from_numpy(v) for k, v in b.items()}
-    out = _net(cfg)(_to(batch))
+    weights = derive_weights(load_weights(), rule) if rule else load_weights()
+    from enerf_amd.network import Network
+    net = Network(cfg)
+    net.load_state_dict(weights, strict=False)
+    out = net.to(_dev()).eval()(_to(batch))
     with torch.no_grad():
-        ref = O.forward(cfg, load_weights(), batch)
+        ref = O.forward(cfg, weights, batch)
+    assert sorted(out) == sorted(ref)
     for k in ref:
         assert _rel(out[k].cpu(), ref[k]) < REL_TOL, (k, _rel(out[k].cpu(), ref[k]))
-    assert O.psnr(out["rgb_level1"].cpu(), ref["rgb_level1"]) > 70.0
+    assert O.psnr(out[f"rgb_level{last}"].cpu(), ref[f"rgb_level{last}"]) > 70.0
 
 
 def test_full_size_dtu_eval_vs_oracle_and_properties():

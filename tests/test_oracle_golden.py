@@ -18,11 +18,11 @@ def weights():
 
 
 @pytest.mark.parametrize("name", list(CASES))
-def test_oracle_matches_reference_outputs(name, weights):
+def test_oracle_matches_reference_outputs(name):
     cfg, batch, gold = case_config(name), case_batch(name), load_golden(name)
     mids = {}
     with torch.no_grad():
-        out = O.forward(cfg, weights, batch, intermediates=mids)
+        out = O.forward(cfg, load_weights(name), batch, intermediates=mids)
     ref_keys = sorted(k[4:] for k in gold if k.startswith("out/"))
     assert sorted(out) == ref_keys
     for k in ref_keys:
