@@ -567,6 +567,97 @@ int enerf_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask
                      out, (hipStream_t)stream);
     return check_launch("eval_ssim");
 }
+// ---- evaluator LPIPS (csrc/lpips_vgg.h) ----
+// the rectangle of the three host-known modes -> {y0, x0, rh, rw}; everything that can be refused without touching the device
+static int eval_lpips_rect(const char* who, int mask_elem_bytes, int mask_mode, int has_mask, int B, int img_h, int img_w,
+                           int rect_mode, int a, int b, int c, int d, int* rect) {
+    REQUIRE(B > 0 && img_h > 0 && img_w > 0, "%s: bad arguments (B, img_h, img_w must be positive)", who);
+    REQUIRE(mask_mode == ENERF_SSIM_MASK_GE1 || mask_mode == ENERF_SSIM_MASK_EQ1, "%s: mask_mode must be 0 (>= 1) or 1 (== 1)", who);
+    if (has_mask) REQUIRE(mask_elem_bytes == 1 || mask_elem_bytes == 4, "%s: mask must be uint8/bool or int32", who);
+    int y0 = 0, x0 = 0, rh = img_h, rw = img_w;
+    if (rect_mode == ENERF_SSIM_RECT_CROP) {
+        REQUIRE(a >= 0 && b >= 0, "%s: negative crop", who);
+        y0 = a; x0 = b; rh = (int)(img_h - 2LL * a); rw = (int)(img_w - 2LL * b);
+    } else if (rect_mode == ENERF_LPIPS_RECT_XYWH) {
+        x0 = a; y0 = b; rw = c; rh = d;
+        REQUIRE(x0 >= 0 && y0 >= 0 && rw > 0 && rh > 0 && (long long)x0 + rw <= img_w && (long long)y0 + rh <= img_h,
+                "%s: rectangle x %d y %d w %d h %d lies outside the %dx%d image", who, x0, y0, rw, rh, img_h, img_w);
+    } else {
+        REQUIRE(rect_mode == ENERF_SSIM_RECT_NONE, "%s: rect_mode must be 0 (whole image), 1 (centre crop) or 3 (x, y, w, h)", who);
+    }
+    REQUIRE(rh >= 16 && rw >= 16, "%s: unsupported rectangle %dx%d: under 16 pixels the fourth pool leaves nothing for relu5_3", who, rh, rw);
+    REQUIRE((long long)2 * B * rh * rw * 64 < (1LL << 31) * 4 && 2 * B <= 65535, "%s: batch too large", who);
+    rect[0] = y0; rect[1] = x0; rect[2] = rh; rect[3] = rw;
+    return ENERF_OK;
+}
+long long enerf_lpips_packed_floats(void) { return lpips_packed_floats(); }
+int enerf_lpips_pack(const enerf_lpips_raw_t* raw, float* packed, enerf_stream_t stream) {
+    REQUIRE(raw && packed, "lpips_pack: null pointer");
+    for (int i = 0; i < kVggLayers; ++i) REQUIRE(raw->conv[i].w && raw->conv[i].b, "lpips_pack: conv %d has a null pointer", i);
+    for (int l = 0; l < 5; ++l) REQUIRE(raw->lin[l], "lpips_pack: lin%d is null", l);
+    launch_lpips_pack(*raw, packed, (hipStream_t)stream);
+    return check_launch("lpips_pack");
+}
+size_t enerf_eval_lpips_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d) {
+    int r[4];
+    if (eval_lpips_rect("eval_lpips", 1, 0, 1, B, img_h, img_w, rect_mode, a, b, c, d, r) != ENERF_OK) return 0;
+    return eval_lpips_workspace_bytes(B, r[2], r[3]);
+}
+int enerf_eval_lpips(const float* packed, const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes,
+                     int mask_mode, int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d, void* workspace,
+                     size_t workspace_bytes, double* out, enerf_stream_t stream) {
+    REQUIRE(packed && pred_rgb && gt_rgb && workspace && out, "eval_lpips: null pointer");
+    REQUIRE(((size_t)workspace & 15) == 0 && ((size_t)out & 7) == 0 && ((size_t)packed & 15) == 0,
+            "eval_lpips: packed and workspace must be 16-byte aligned, out 8-byte aligned");
+    int r[4];
+    const int rc = eval_lpips_rect("eval_lpips", mask_elem_bytes, mask_mode, mask != nullptr, B, img_h, img_w, rect_mode, a, b, c, d, r);
+    if (rc != ENERF_OK) return rc;
+    const size_t need = eval_lpips_workspace_bytes(B, r[2], r[3]);
+    if (workspace_bytes < need) return fail(ENERF_EWORKSPACE, "eval_lpips: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    const VggFront f = {pred_rgb, gt_rgb, (const unsigned char*)mask, mask_elem_bytes, mask_mode, B, img_h, img_w, r[0], r[1]};
+    launch_eval_lpips(packed, f, r[2], r[3], workspace, out, (hipStream_t)stream);
+    return check_launch("eval_lpips");
+}
+int enerf_lpips_front(const float* packed, const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes,
+                      int mask_mode, int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d, float* out_cl,
+                      enerf_stream_t stream) {
+    REQUIRE(packed && pred_rgb && gt_rgb && out_cl, "lpips_front: null pointer");
+    REQUIRE(((size_t)out_cl & 15) == 0 && ((size_t)packed & 15) == 0, "lpips_front: packed and out_cl must be 16-byte aligned");
+    int r[4];
+    const int rc = eval_lpips_rect("lpips_front", mask_elem_bytes, mask_mode, mask != nullptr, B, img_h, img_w, rect_mode, a, b, c, d, r);
+    if (rc != ENERF_OK) return rc;
+    const VggFront f = {pred_rgb, gt_rgb, (const unsigned char*)mask, mask_elem_bytes, mask_mode, B, img_h, img_w, r[0], r[1]};
+    launch_vgg_conv3x3(packed, 3, 64, nullptr, out_cl, 2 * B, r[2], r[3], 0, r[2], r[3], 1, &f, (hipStream_t)stream);
+    return check_launch("lpips_front");
+}
+long long enerf_vgg_conv3x3_packed_floats(int cin, int cout) {
+    return vgg_conv3x3_supported(cin, cout) ? vgg_conv3x3_packed_floats(cin, cout) : 0;
+}
+int enerf_vgg_conv3x3_pack(const float* w, const float* b, int cin, int cout, float* packed, enerf_stream_t stream) {
+    REQUIRE(w && b && packed, "vgg_conv3x3_pack: null pointer");
+    REQUIRE(vgg_conv3x3_supported(cin, cout), "vgg_conv3x3_pack: unsupported layer %d -> %d (not a VGG16 pair)", cin, cout);
+    launch_vgg_conv3x3_pack(w, b, cin, cout, packed, (hipStream_t)stream);
+    return check_launch("vgg_conv3x3_pack");
+}
+int enerf_vgg_conv3x3(const float* packed_layer, int cin, int cout, const float* in_cl, float* out_cl, int N, int H, int W,
+                      int relu, enerf_stream_t stream) {
+    REQUIRE(packed_layer && in_cl && out_cl, "vgg_conv3x3: null pointer");
+    REQUIRE(vgg_conv3x3_supported(cin, cout), "vgg_conv3x3: unsupported layer %d -> %d (not a VGG16 pair)", cin, cout);
+    REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W * (cin > cout ? cin : cout) < (1LL << 31) * 4,
+            "vgg_conv3x3: bad shape (N %d, H %d, W %d)", N, H, W);
+    REQUIRE(((size_t)packed_layer & 15) == 0 && ((size_t)out_cl & 15) == 0 && (cin == 3 || ((size_t)in_cl & 15) == 0),
+            "vgg_conv3x3: packed_layer, in_cl and out_cl must be 16-byte aligned");
+    launch_vgg_conv3x3(packed_layer, cin, cout, in_cl, out_cl, N, H, W, 0, H, W, relu, nullptr, (hipStream_t)stream);
+    return check_launch("vgg_conv3x3");
+}
+int enerf_mask_bbox(const void* mask, int elem_bytes, int mask_mode, int B, int h, int w, int* rect, enerf_stream_t stream) {
+    REQUIRE(mask && rect, "mask_bbox: null pointer");
+    REQUIRE(elem_bytes == 1 || elem_bytes == 4, "mask_bbox: mask must be uint8/bool or int32");
+    REQUIRE(mask_mode == ENERF_SSIM_MASK_GE1 || mask_mode == ENERF_SSIM_MASK_EQ1, "mask_bbox: mask_mode must be 0 (>= 1) or 1 (== 1)");
+    REQUIRE(B > 0 && B <= 65535 && h > 0 && w > 0, "mask_bbox: bad shape");
+    launch_mask_bbox(mask, elem_bytes, mask_mode, B, h, w, rect, (hipStream_t)stream);
+    return check_launch("mask_bbox");
+}
 int enerf_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                       enerf_stream_t stream) {
     REQUIRE(tar_ext && tar_ixt && xy && rays && B > 0 && N >= 0 && scale > 0.f, "gen_rays_at: bad arguments");

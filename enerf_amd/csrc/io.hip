@@ -2,8 +2,8 @@
 //   before: full-image ray generation (lib/datasets/enerf_utils.py:61-71, numpy on the host today; 10.5 MB of
 //           rays_1 per 512x640 frame would otherwise cross PCIe every frame)
 //   after:  uint8 packing + vertical flip for presentation (gui_human.py:88-91) and the evaluator's masked
-//           PSNR / depth statistics (lib/evaluators/enerf.py:67-71, 88-103) and SSIM (:76, enerf_human.py:54-66) without a
-//           D2H copy of fp32 images.
+//           PSNR / depth statistics (lib/evaluators/enerf.py:67-71, 88-103), SSIM (:76, enerf_human.py:54-66) and LPIPS (:81-87;
+//           lpips_vgg.h, included at the end: the one MFMA kernel here) without a D2H copy of fp32 images.
 // All HBM-bound, one thread per output element — except the SSIM kernels at the end (LDS tiles, float64 window sums).
 #include "kernels.h"
 
@@ -483,3 +483,6 @@ void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* ma
 }
 
 }  // namespace enerf
+
+// Evaluator LPIPS (evaluators/enerf.py:81-87, enerf_human.py:71-77): the VGG16 trunk and the taps
+#include "lpips_vgg.h"

@@ -221,6 +221,26 @@ size_t eval_ssim_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int
 void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_bytes, int mask_mode, int B,
                       int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
                       hipStream_t st);
+// LPIPS of the evaluators (lpips_vgg.h, included by io.hip): the VGG16 trunk as 3x3 fp32-MFMA convolutions + the five taps.
+// pool: a 2x2 / stride 2 / floor max pool in front of the layer; tap: the tap taken after it, or -1
+struct VggLayerSpec { int cin, cout, pool, tap; };
+constexpr int kVggLayers = 13;
+constexpr VggLayerSpec kVggSpec[kVggLayers] = {{3, 64, 0, -1},   {64, 64, 0, 0},    {64, 128, 1, -1},  {128, 128, 0, 1}, {128, 256, 1, -1},
+                                               {256, 256, 0, -1}, {256, 256, 0, 2},  {256, 512, 1, -1}, {512, 512, 0, -1}, {512, 512, 0, 3},
+                                               {512, 512, 1, -1}, {512, 512, 0, -1}, {512, 512, 0, 4}};
+constexpr int kLpipsTapC[5] = {64, 128, 256, 512, 512};
+// conv 0 reading the evaluator's images: pred / gt (B, img_h*img_w, 3), the mask as enerf_eval_ssim takes it, the rectangle's corner
+struct VggFront { const float* pred; const float* gt; const unsigned char* mask; int mask_bytes, mask_mode, B, img_h, img_w, y0, x0; };
+bool vgg_conv3x3_supported(int cin, int cout);
+long long vgg_conv3x3_packed_floats(int cin, int cout);
+void launch_vgg_conv3x3_pack(const float* w, const float* bias, int cin, int cout, float* packed, hipStream_t st);
+void launch_vgg_conv3x3(const float* packed_layer, int cin, int cout, const float* in, float* out, int N, int H, int W, int pool,
+                        int Hin, int Win, int relu, const VggFront* front, hipStream_t st);
+long long lpips_packed_floats();
+void launch_lpips_pack(const enerf_lpips_raw_t& raw, float* packed, hipStream_t st);
+size_t eval_lpips_workspace_bytes(int B, int rh, int rw);
+void launch_eval_lpips(const float* packed, const VggFront& front, int rh, int rw, void* workspace, double* out, hipStream_t st);
+void launch_mask_bbox(const void* mask, int mask_bytes, int mask_mode, int B, int img_h, int img_w, int* rect, hipStream_t st);
 void launch_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                         hipStream_t st);
 void launch_rays_bbox_mask(const float* rays, const float* bounds, long long n, int* mask, hipStream_t st);

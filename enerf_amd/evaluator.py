@@ -6,8 +6,10 @@ Mirrors the part of ``lib/evaluators/enerf.py`` the hot path can serve: masked /
 one 48-byte D2H copy per (frame, level) instead of the fp32 images.  With ``eval_ssim=True`` the evaluators' second number, SSIM
 (:76: skimage's ``structural_similarity(gt, pred, multichannel=True)`` on the mask-zeroed, centre-cropped images), comes from
 ``enerf_eval_ssim`` in the same way and the copy grows to 64 bytes.  ``DeviceEvaluatorHuman`` is the counterpart of
-``lib/evaluators/enerf_human.py`` (``mask_at_box`` at the last level, SSIM on the mask's bounding rectangle).  LPIPS stays where
-it is (the lpips package and its VGG weights).
+``lib/evaluators/enerf_human.py`` (``mask_at_box`` at the last level, SSIM on the mask's bounding rectangle).  With
+``eval_lpips=LpipsWeights`` the third number, LPIPS (:81-87: ``lpips.LPIPS(net='vgg')`` on the same mask-zeroed, cropped images), comes
+from ``enerf_eval_lpips`` (the VGG16 trunk as fp32-MFMA HIP kernels) and the same copy grows by 48 bytes.  The package ships the
+code, not the network's weights: those are the user's (``enerf_amd.lpips.LpipsWeights.from_state_dict``).
 """
 from __future__ import annotations
 
@@ -17,6 +19,9 @@ import torch
 
 from .config import EnerfConfig
 from .lib import EnerfLib, get_lib, stats_from_acc
+from .lpips import LpipsWeights
+
+LPIPS_MIN_EXTENT = 16      # under 16 pixels the fourth pool leaves nothing for relu5_3: such a level's lpips is NaN
 
 
 def nearest_resize_index(src: int, dst: int, device) -> torch.Tensor:
@@ -29,8 +34,9 @@ def nearest_resize_index(src: int, dst: int, device) -> torch.Tensor:
 
 class DeviceEvaluator:
     def __init__(self, cfg: EnerfConfig, eval_center: bool = False, eval_depth: bool = False,
-                 lib: Optional[EnerfLib] = None, eval_ssim: bool = False):
+                 lib: Optional[EnerfLib] = None, eval_ssim: bool = False, eval_lpips: Optional[LpipsWeights] = None):
         self.cfg, self.eval_center, self.eval_depth, self.eval_ssim = cfg, eval_center, eval_depth, eval_ssim
+        self.eval_lpips = eval_lpips
         self._lib = lib
         self.reset()
 
@@ -39,6 +45,8 @@ class DeviceEvaluator:
         self.level_psnrs: Dict[int, List[float]] = {}
         self.ssims: List[float] = []
         self.level_ssims: Dict[int, List[float]] = {}
+        self.lpips: List[float] = []
+        self.level_lpips: Dict[int, List[float]] = {}
         self.abs, self.acc_2, self.acc_10 = [], [], []
         self.mvs_abs, self.mvs_acc_2, self.mvs_acc_10 = [], [], []
 
@@ -66,7 +74,7 @@ class DeviceEvaluator:
                 if self.eval_depth and last and "tar_dpt" in batch:
                     depth_args = dict(pred_depth=output[f"depth_level{i}"][b].contiguous(),
                                       gt_depth=batch["tar_dpt"][b].reshape(-1).contiguous())
-                if self.eval_ssim:
+                if self.eval_ssim or self.eval_lpips is not None:
                     st = self._stats_and_ssim(i, last, pred, gt, mask, (h, w), crop, depth_args)
                 else:
                     st = self.lib.eval_stats(pred, gt, mask, image_hw=(h, w), crop=crop, **depth_args)
@@ -89,13 +97,31 @@ class DeviceEvaluator:
                             self.mvs_abs.append(ms["abs"]); self.mvs_acc_2.append(ms["acc_2"]); self.mvs_acc_10.append(ms["acc_10"])
 
     def _stats_and_ssim(self, level, last, pred, gt, mask, hw, crop, depth_args, bbox=False, mask_is_one=False) -> dict:
-        """psnr / depth accumulator and SSIM of one image: two enqueued calls, ONE blocking 64-byte D2H copy for both."""
-        acc = self.lib.eval_stats(pred, gt, mask, image_hw=hw, crop=crop, sync=False, **depth_args)
-        ss = self.lib.eval_ssim(pred, gt, mask, image_hw=hw, crop=crop, bbox=bbox, mask_is_one=mask_is_one, sync=False)
-        both = torch.cat([acc, ss.reshape(-1)]).cpu().tolist()
-        self.level_ssims.setdefault(level, []).append(both[6])
-        if last:
-            self.ssims.append(both[6])
+        """psnr / depth accumulator, SSIM and LPIPS of one image: up to three enqueued calls, ONE blocking D2H copy for all of them
+        (48 bytes, + 16 with SSIM, + 48 with LPIPS).  LPIPS needs its rectangle on the host (it fixes the launch geometry of
+        thirteen layers): with ``bbox`` that is one more small blocking copy per image, the 16 bytes of ``mask_bbox``."""
+        parts = [self.lib.eval_stats(pred, gt, mask, image_hw=hw, crop=crop, sync=False, **depth_args)]
+        if self.eval_ssim:
+            parts.append(self.lib.eval_ssim(pred, gt, mask, image_hw=hw, crop=crop, bbox=bbox, mask_is_one=mask_is_one,
+                                            sync=False).reshape(-1))
+        too_small = False
+        if self.eval_lpips is not None:
+            rect = self.lib.mask_bbox(mask, hw, mask_is_one=mask_is_one)[0] if bbox else None
+            rh, rw = (rect[3], rect[2]) if bbox else (hw[0] - 2 * crop[0], hw[1] - 2 * crop[1])
+            too_small = rh < LPIPS_MIN_EXTENT or rw < LPIPS_MIN_EXTENT
+            if not too_small:
+                parts.append(self.lib.eval_lpips(self.eval_lpips.packed(self.lib), pred, gt, mask, image_hw=hw, crop=crop, rect=rect,
+                                                 mask_is_one=mask_is_one, sync=False).reshape(-1))
+        both = torch.cat(parts).cpu().tolist()
+        if self.eval_ssim:
+            self.level_ssims.setdefault(level, []).append(both[6])
+            if last:
+                self.ssims.append(both[6])
+        if self.eval_lpips is not None:
+            lp = float("nan") if too_small else both[-6]
+            self.level_lpips.setdefault(level, []).append(lp)
+            if last:
+                self.lpips.append(lp)
         return stats_from_acc(both[:6])
 
     def summarize(self) -> dict:
@@ -105,6 +131,9 @@ class DeviceEvaluator:
         if self.eval_ssim:
             ret["ssim"] = mean(self.ssims)
             ret.update({f"ssim_level{i}": mean(v) for i, v in self.level_ssims.items()})
+        if self.eval_lpips is not None:
+            ret["lpips"] = mean(self.lpips)
+            ret.update({f"lpips_level{i}": mean(v) for i, v in self.level_lpips.items()})
         if self.abs:
             ret.update(abs=mean(self.abs), acc_2=mean(self.acc_2), acc_10=mean(self.acc_10))
         if self.mvs_abs:                 # the reference accumulates these (:101-103) but never prints them; reported here
@@ -117,10 +146,12 @@ class DeviceEvaluatorHuman(DeviceEvaluator):
     """``lib/evaluators/enerf_human.py:29-84`` on the device: the mask is ``mask_at_box`` at the last cascade level and all ones
     at the others (:39-42), selected by ``== 1`` (:54); psnr over the selected pixels (:58); SSIM on the selected pixels'
     bounding rectangle with everything else zeroed (:55-56,64-66).  The rectangle is found on the device.  ``summarize()``
-    returns ``psnr``, ``ssim`` (last level) and both per rendered level; no depth statistics, as in the reference."""
+    returns ``psnr``, ``ssim`` (last level) and both per rendered level; no depth statistics, as in the reference.  With
+    ``eval_lpips=LpipsWeights`` also ``lpips`` (:71-77) on the same rectangle: the device-found rectangle fixes every later launch
+    geometry, so it is read back first — one more small blocking copy (16 bytes) per masked image."""
 
-    def __init__(self, cfg: EnerfConfig, lib: Optional[EnerfLib] = None):
-        super().__init__(cfg, eval_center=False, eval_depth=False, lib=lib, eval_ssim=True)
+    def __init__(self, cfg: EnerfConfig, lib: Optional[EnerfLib] = None, eval_lpips: Optional[LpipsWeights] = None):
+        super().__init__(cfg, eval_center=False, eval_depth=False, lib=lib, eval_ssim=True, eval_lpips=eval_lpips)
 
     def evaluate(self, output: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]):
         cas = self.cfg.cas

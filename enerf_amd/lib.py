@@ -128,6 +128,22 @@ class SourceCacheStruct(C.Structure):
 SOURCE_CACHE_BUFFERS = 5 + MAX_LEVELS
 
 
+class _ConvWB(C.Structure):
+    _fields_ = [("w", _f), ("b", _f)]
+
+
+class LpipsRaw(C.Structure):
+    """``enerf_lpips_raw_t``."""
+    _fields_ = [("conv", _ConvWB * 13), ("lin", _f * 5)]
+
+
+# the VGG16 trunk of LPIPS: (cin, cout) of features.{0,2,5,7,10,12,14,17,19,21,24,26,28}, the tap widths, the rect modes
+VGG_CONVS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+             (512, 512), (512, 512), (512, 512))
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
+RECT_NONE, RECT_CROP, RECT_XYWH = 0, 1, 3
+
+
 def cascade_struct(cfg) -> Cascade:
     """EnerfConfig -> enerf_cascade_t."""
     cas = cfg.cas
@@ -237,6 +253,15 @@ _SIGNATURES = {
     "enerf_eval_stats": (_i, [_f, _f, C.c_void_p, _i, _ll, _i, _i, _i, _i, _f, _f, _ll, _f, _f]),
     "enerf_eval_ssim_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "enerf_eval_ssim": (_i, [_f, _f, C.c_void_p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_void_p, C.c_void_p, _f]),
+    "enerf_lpips_packed_floats": (_ll, []),
+    "enerf_lpips_pack": (_i, [C.POINTER(LpipsRaw), _f, _f]),
+    "enerf_eval_lpips_workspace_bytes": (C.c_size_t, [_i] * 8),
+    "enerf_eval_lpips": (_i, [_f, _f, _f, C.c_void_p, _i, _i] + [_i] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p, _f]),
+    "enerf_lpips_front": (_i, [_f, _f, _f, C.c_void_p, _i, _i] + [_i] * 8 + [_f, _f]),
+    "enerf_vgg_conv3x3_packed_floats": (_ll, [_i, _i]),
+    "enerf_vgg_conv3x3_pack": (_i, [_f, _f, _i, _i, _f, _f]),
+    "enerf_vgg_conv3x3": (_i, [_f, _i, _i, _f, _f, _i, _i, _i, _i, _f]),
+    "enerf_mask_bbox": (_i, [C.c_void_p, _i, _i, _i, _i, _i, C.c_void_p, _f]),
     "enerf_gen_rays_at": (_i, [_f, _f, C.c_void_p, _i, _i, _fl, _f, _f]),
     "enerf_rays_bbox_mask": (_i, [_f, _f, _ll, C.c_void_p, _f]),
     "enerf_select_views": (_i, [_f, _i, _f, _i, C.c_void_p, _f]),
@@ -1238,6 +1263,116 @@ class EnerfLib:
         if not sync:
             return out
         return out.cpu()[:, 0].tolist()
+
+    # -- evaluator LPIPS (csrc/lpips_vgg.h) ------------------------------------------------------------
+    def lpips_pack(self, convs, lins):
+        """``convs``: thirteen (w (cout,cin,3,3), b (cout)) pairs in trunk order, ``lins``: five (C_l) tensors -> the packed image
+        ``enerf_eval_lpips`` reads (``enerf_amd.lpips.LpipsWeights`` builds these lists)."""
+        if len(convs) != 13 or len(lins) != 5:
+            raise EnerfError("lpips_pack needs 13 (w, b) pairs and 5 lin vectors")
+        raw = LpipsRaw()
+        for i, ((w, b), (cin, cout)) in enumerate(zip(convs, VGG_CONVS)):
+            if tuple(w.shape) != (cout, cin, 3, 3) or tuple(b.shape) != (cout,):
+                raise EnerfError(f"lpips_pack: conv {i} must be ({cout},{cin},3,3) + ({cout},), got {tuple(w.shape)} + {tuple(b.shape)}")
+            raw.conv[i].w, raw.conv[i].b = _ptr(w), _ptr(b)
+        for l, (v, c) in enumerate(zip(lins, LPIPS_TAP_CHANNELS)):
+            if v.numel() != c:
+                raise EnerfError(f"lpips_pack: lin{l} must hold {c} values, got {tuple(v.shape)}")
+            raw.lin[l] = _ptr(v)
+        dev = convs[0][0].device
+        packed = torch.empty((self.dll.enerf_lpips_packed_floats(),), dtype=torch.float32, device=dev)
+        self._check(self.dll.enerf_lpips_pack(C.byref(raw), _ptr(packed), self.stream_of(packed)), "lpips_pack")
+        return packed
+
+    def _lpips_args(self, what, pred_rgb, gt_rgb, mask, image_hw, crop, rect):
+        if image_hw is None:
+            raise EnerfError(f"{what} needs image_hw=(h, w)")
+        h, w = int(image_hw[0]), int(image_hw[1])
+        if h <= 0 or w <= 0 or pred_rgb.numel() == 0 or pred_rgb.numel() % (h * w * 3) or gt_rgb.numel() != pred_rgb.numel():
+            raise EnerfError(f"{what}: pred / gt must be (B, {h}*{w}, 3) tensors of the same size")
+        B = pred_rgb.numel() // (h * w * 3)
+        mb = 0
+        if mask is not None:
+            if mask.dtype not in (torch.int32, torch.uint8, torch.bool) or not mask.is_contiguous():
+                raise EnerfError("mask must be a contiguous int32 / uint8 / bool tensor")
+            if mask.numel() != B * h * w:
+                raise EnerfError(f"{what}: mask has {mask.numel()} elements, the images {B * h * w} pixels")
+            mb = mask.element_size()
+        if rect is not None:
+            mode, abcd = RECT_XYWH, tuple(int(v) for v in rect)
+            if len(abcd) != 4:
+                raise EnerfError(f"{what}: rect must be (x, y, w, h)")
+        elif (int(crop[0]), int(crop[1])) != (0, 0):
+            mode, abcd = RECT_CROP, (int(crop[0]), int(crop[1]), 0, 0)
+        else:
+            mode, abcd = RECT_NONE, (0, 0, 0, 0)
+        return h, w, B, mb, mode, abcd
+
+    def eval_lpips(self, packed, pred_rgb, gt_rgb, mask=None, image_hw=None, crop=(0, 0), rect=None, mask_is_one=False, sync=True):
+        """``loss_fn_vgg(pred, gt)`` of evaluators/enerf.py:81-87 / enerf_human.py:71-77 (lpips.LPIPS(net='vgg')) on device, with the
+        evaluators' preprocessing: pixels whose ``mask`` is off (``>= 1`` is on; ``== 1`` with ``mask_is_one``) count as 0, the
+        image is the ``eval_center`` slice ``crop`` = (crop_h, crop_w) or the rectangle ``rect`` = (x, y, w, h) (host values: for the
+        human evaluator, ``mask_bbox`` read back), then (x - 0.5) * 2.  ``packed``: ``lpips_pack``'s image (the weights are the
+        caller's).  ``pred_rgb`` / ``gt_rgb``: (B, h*w, 3) or (h*w, 3) with ``image_hw`` = (h, w).  Returns one float per image after
+        ONE 48*B-byte D2H copy — or, with ``sync=False``, the (B,6) float64 device tensor {lpips, d_0 .. d_4}; nothing synchronises
+        then.  A rectangle under 16 pixels in either extent, or outside the image, raises."""
+        h, w, B, mb, mode, abcd = self._lpips_args("eval_lpips", pred_rgb, gt_rgb, mask, image_hw, crop, rect)
+        pp, gp, kp = _ptr(pred_rgb), _ptr(gt_rgb), _ptr(packed)
+        nbytes = self.dll.enerf_eval_lpips_workspace_bytes(B, h, w, mode, *abcd)
+        if nbytes == 0:
+            raise EnerfError(f"eval_lpips failed: {self.dll.enerf_last_error().decode()}")
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=pred_rgb.device)
+        out = torch.empty((B, 6), dtype=torch.float64, device=pred_rgb.device)
+        self._check(self.dll.enerf_eval_lpips(kp, pp, gp, None if mask is None else mask.data_ptr(), mb, int(bool(mask_is_one)), B, h, w,
+                                              mode, *abcd, ws.data_ptr(), nbytes, out.data_ptr(), self.stream_of(pred_rgb)), "eval_lpips")
+        if not sync:
+            return out
+        return out.cpu()[:, 0].tolist()
+
+    def lpips_front(self, packed, pred_rgb, gt_rgb, mask=None, image_hw=None, crop=(0, 0), rect=None, mask_is_one=False):
+        """The first layer of ``eval_lpips`` alone (preprocessing, scaling layer, conv 0 + ReLU): (2B, rh, rw, 64) channels-last,
+        the pred images first, then the gt images."""
+        h, w, B, mb, mode, abcd = self._lpips_args("lpips_front", pred_rgb, gt_rgb, mask, image_hw, crop, rect)
+        rh, rw = (abcd[3], abcd[2]) if mode == RECT_XYWH else (h - 2 * abcd[0], w - 2 * abcd[1])
+        out = torch.empty((2 * B, max(rh, 1), max(rw, 1), 64), dtype=torch.float32, device=pred_rgb.device)
+        self._check(self.dll.enerf_lpips_front(_ptr(packed), _ptr(pred_rgb), _ptr(gt_rgb), None if mask is None else mask.data_ptr(), mb,
+                                               int(bool(mask_is_one)), B, h, w, mode, *abcd, _ptr(out), self.stream_of(pred_rgb)),
+                    "lpips_front")
+        return out
+
+    def vgg_conv3x3_pack(self, w, b):
+        """w (cout,cin,3,3), b (cout) of one VGG16 layer -> its packed image (A operands | bias)."""
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        n = self.dll.enerf_vgg_conv3x3_packed_floats(cin, cout)
+        if n == 0 or tuple(w.shape[2:]) != (3, 3) or tuple(b.shape) != (cout,):
+            raise EnerfError(f"vgg_conv3x3_pack: unsupported layer {tuple(w.shape)} + {tuple(b.shape)} (not a VGG16 3x3 pair)")
+        packed = torch.empty((n,), dtype=torch.float32, device=w.device)
+        self._check(self.dll.enerf_vgg_conv3x3_pack(_ptr(w), _ptr(b), cin, cout, _ptr(packed), self.stream_of(w)), "vgg_conv3x3_pack")
+        return packed
+
+    def vgg_conv3x3(self, packed_layer, cin, cout, x_cl, relu=True):
+        """One trunk layer on a channels-last tensor: x_cl (N,H,W,cin) -> (N,H,W,cout); 3x3, stride 1, zero padding 1, bias, ReLU."""
+        if x_cl.dim() != 4 or x_cl.shape[3] != cin:
+            raise EnerfError(f"vgg_conv3x3: input must be (N,H,W,{cin}) channels-last, got {tuple(x_cl.shape)}")
+        N, H, W, _ = x_cl.shape
+        out = torch.empty((N, H, W, cout), dtype=torch.float32, device=x_cl.device)
+        self._check(self.dll.enerf_vgg_conv3x3(_ptr(packed_layer), int(cin), int(cout), _ptr(x_cl), _ptr(out), N, H, W, int(bool(relu)),
+                                               self.stream_of(x_cl)), "vgg_conv3x3")
+        return out
+
+    def mask_bbox(self, mask, image_hw, mask_is_one=False, sync=True):
+        """cv2.boundingRect of the on pixels (enerf_human.py:64) per image: mask (B, h*w) -> (B,4) int32 {x, y, w, h} (all 0: nothing
+        on).  ``sync=True`` returns a list of tuples after a 16*B-byte D2H copy; ``sync=False`` the device tensor."""
+        h, w = int(image_hw[0]), int(image_hw[1])
+        if mask.dtype not in (torch.int32, torch.uint8, torch.bool) or not mask.is_contiguous() or mask.numel() % (h * w):
+            raise EnerfError("mask must be a contiguous int32 / uint8 / bool tensor of B*h*w elements")
+        B = mask.numel() // (h * w)
+        rect = torch.empty((B, 4), dtype=torch.int32, device=mask.device)
+        self._check(self.dll.enerf_mask_bbox(mask.data_ptr(), mask.element_size(), int(bool(mask_is_one)), B, h, w, rect.data_ptr(),
+                                             self.stream_of(mask)), "mask_bbox")
+        if not sync:
+            return rect
+        return [tuple(r) for r in rect.cpu().tolist()]
 
     def depth_stats(self, pred_depth, gt_depth, sync=True):
         """The depth statistics alone (evaluators/enerf.py:96-103: abs / acc_2 / acc_10 over gt != 0): enerf_eval_stats with

@@ -646,6 +646,54 @@ int enerf_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* mask
                     int img_h, int img_w, int rect_mode, int crop_h, int crop_w, void* workspace, double* out,
                     enerf_stream_t stream);
 
+/* ---- evaluator LPIPS on the device (ABI v11 grew by these entries; new symbols only, the version number is unchanged) ----
+ * enerf_eval_lpips replaces `loss_fn_vgg(pred, gt)` of lib/evaluators/enerf.py:81-87 and enerf_human.py:71-77
+ * (lpips.LPIPS(net='vgg'): lpips=True, spatial=False, eval mode) together with the preprocessing in front of it (enerf.py:48-54,
+ * 67-69,82-83; enerf_human.py:54-56,64,72-73): pixels whose mask is off are set to 0, the image is the eval_center slice or the
+ * mask's bounding rectangle, then (x - 0.5) * 2, lpips' scaling layer, the torchvision VGG16 `features` trunk (thirteen 3x3 convs
+ * with bias + ReLU, four 2x2 floor max pools) and the five taps after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3:
+ * d_l = mean over pixels of sum_c lin_l[c] * (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, lpips = sum_l d_l.  The convolutions
+ * are exact-fp32 MFMA kernels (csrc/lpips_vgg.h); the taps accumulate in float64.  No weights ship with the library: the caller packs
+ * their own (enerf_lpips_pack).
+ *   enerf_lpips_raw_t            torch-layout device pointers: conv[i] = {w (cout,cin,3,3), b (cout)} of features.{0,2,5,7,10,12,14,
+ *                                17,19,21,24,26,28}; lin[l] (C_l) = the (1,C_l,1,1) weight of lin{l}, C = 64,128,256,512,512
+ *   enerf_lpips_packed_floats    floats of the packed image;  enerf_lpips_pack builds it (A-operand images | biases | lin)
+ *   enerf_eval_lpips             pred_rgb / gt_rgb / mask / mask_elem_bytes / mask_mode as enerf_eval_ssim.  rect_mode:
+ *       ENERF_SSIM_RECT_NONE the whole image; ENERF_SSIM_RECT_CROP the eval_center slice (a, b = crop_h, crop_w);
+ *       ENERF_LPIPS_RECT_XYWH the rectangle a..d = x, y, w, h, known on the host (enerf_human.py:64: the caller reads
+ *       enerf_mask_bbox's 16 bytes back; the rectangle fixes every launch geometry).  All B images share the rectangle.
+ *       out (B,6) doubles {lpips, d_0 .. d_4}, lpips = (((d_0 + d_1) + d_2) + d_3) + d_4; bit-identical from call to call (no
+ *       floating-point atomics, partial sums added in a fixed order); pred == gt gives exactly 0.  Only enqueues: no host sync.
+ *       A rectangle under 16 pixels in either extent cannot reach relu5_3, one outside the image cannot be read: ENERF_EINVAL
+ *       before anything is launched (the size query returns 0).  workspace: enerf_eval_lpips_workspace_bytes(...) bytes, 16-byte
+ *       aligned (tap partials | two ping-pong activation buffers of (2B, rh, rw, 64) floats); too small: ENERF_EWORKSPACE.
+ *   enerf_lpips_front            the first layer alone as enerf_eval_lpips runs it (preprocessing, scaling layer, conv 0 + ReLU):
+ *       out_cl (2B, rh, rw, 64) channels-last, pred images first, then gt.
+ *   enerf_vgg_conv3x3            one layer of the same kernel on channels-last tensors: in_cl (N,H,W,cin) -> out_cl (N,H,W,cout),
+ *       3x3 / stride 1 / zero padding 1 + bias (+ ReLU); (cin, cout) one of the trunk's pairs (3,64) (64,64) (64,128) (128,128)
+ *       (128,256) (256,256) (256,512) (512,512), else ENERF_EINVAL.  packed_layer: enerf_vgg_conv3x3_pack of w (cout,cin,3,3), b.
+ *   enerf_mask_bbox              cv2.boundingRect of the ON pixels (enerf_human.py:64) per image: rect (B,4) int32 device
+ *       {x, y, w, h}, all 0 when nothing is on. */
+#define ENERF_LPIPS_RECT_XYWH 3
+typedef struct {
+    struct { const float *w, *b; } conv[13];
+    const float* lin[5];
+} enerf_lpips_raw_t;
+long long enerf_lpips_packed_floats(void);
+int enerf_lpips_pack(const enerf_lpips_raw_t* raw, float* packed, enerf_stream_t stream);
+size_t enerf_eval_lpips_workspace_bytes(int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d);
+int enerf_eval_lpips(const float* packed, const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes,
+                     int mask_mode, int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d, void* workspace,
+                     size_t workspace_bytes, double* out, enerf_stream_t stream);
+int enerf_lpips_front(const float* packed, const float* pred_rgb, const float* gt_rgb, const void* mask, int mask_elem_bytes,
+                      int mask_mode, int B, int img_h, int img_w, int rect_mode, int a, int b, int c, int d, float* out_cl,
+                      enerf_stream_t stream);
+long long enerf_vgg_conv3x3_packed_floats(int cin, int cout);
+int enerf_vgg_conv3x3_pack(const float* w, const float* b, int cin, int cout, float* packed, enerf_stream_t stream);
+int enerf_vgg_conv3x3(const float* packed_layer, int cin, int cout, const float* in_cl, float* out_cl, int N, int H, int W,
+                      int relu, enerf_stream_t stream);
+int enerf_mask_bbox(const void* mask, int elem_bytes, int mask_mode, int B, int h, int w, int* rect, enerf_stream_t stream);
+
 /* ---- source-view cache (ABI v11 grew by these five entries; new symbols only, the version number is unchanged) ----
  * A static scene (dtu / llff / nerf test splits) or one time frame of the interactive viewer draws the S source views of every
  * frame from one fixed set of V images: zjumocap/enerf_interactive.py:102-105,138-153 (cache_data) preloads the V views once and
