@@ -658,6 +658,74 @@ int enerf_mask_bbox(const void* mask, int elem_bytes, int mask_mode, int B, int 
     launch_mask_bbox(mask, elem_bytes, mask_mode, B, h, w, rect, (hipStream_t)stream);
     return check_launch("mask_bbox");
 }
+// ---- trainer's perceptual term (csrc/perceptual_vgg.h) ----
+static int perceptual_check_shape(const char* who, int N, int h, int w) {
+    REQUIRE(N > 0 && 2 * (long long)N <= 65535, "%s: N must be 1 .. 32767 image pairs, got %d", who, N);
+    REQUIRE(h >= 8 && w >= 8, "%s: unsupported image %dx%d: under 8 pixels the third pool leaves nothing for relu4_3", who, h, w);
+    REQUIRE((long long)2 * N * h * w * 64 < (1LL << 31) * 4, "%s: batch too large (N %d of %dx%d)", who, N, h, w);
+    return ENERF_OK;
+}
+long long enerf_perceptual_packed_floats(void) { return perceptual_packed_floats(); }
+int enerf_perceptual_pack(const enerf_perceptual_raw_t* raw, float* packed, enerf_stream_t stream) {
+    REQUIRE(raw && packed, "perceptual_pack: null pointer");
+    for (int i = 0; i < 10; ++i) REQUIRE(raw->conv[i].w && raw->conv[i].b, "perceptual_pack: conv %d has a null pointer", i);
+    launch_perceptual_pack(*raw, packed, (hipStream_t)stream);
+    return check_launch("perceptual_pack");
+}
+size_t enerf_perceptual_workspace_bytes(int N, int h, int w) {
+    if (perceptual_check_shape("perceptual_workspace_bytes", N, h, w) != ENERF_OK) return 0;
+    return perceptual_workspace_bytes(N, h, w);
+}
+int enerf_perceptual_layout(int N, int h, int w, long long* offsets) {
+    REQUIRE(offsets, "perceptual_layout: null pointer");
+    const int rc = perceptual_check_shape("perceptual_layout", N, h, w);
+    if (rc != ENERF_OK) return rc;
+    perceptual_layout(N, h, w, offsets);
+    return ENERF_OK;
+}
+int enerf_perceptual_fwd(const float* packed, const float* pred_rgb, const float* gt_rgb, int N, int h, int w, void* workspace,
+                         size_t workspace_bytes, double* out, enerf_stream_t stream) {
+    REQUIRE(packed && pred_rgb && gt_rgb && workspace && out, "perceptual_fwd: null pointer");
+    REQUIRE(((size_t)workspace & 15) == 0 && ((size_t)out & 7) == 0 && ((size_t)packed & 15) == 0,
+            "perceptual_fwd: packed and workspace must be 16-byte aligned, out 8-byte aligned");
+    const int rc = perceptual_check_shape("perceptual_fwd", N, h, w);
+    if (rc != ENERF_OK) return rc;
+    const size_t need = perceptual_workspace_bytes(N, h, w);
+    if (workspace_bytes < need) return fail(ENERF_EWORKSPACE, "perceptual_fwd: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    launch_perceptual_fwd(packed, pred_rgb, gt_rgb, N, h, w, workspace, out, (hipStream_t)stream);
+    return check_launch("perceptual_fwd");
+}
+int enerf_perceptual_bwd(const float* packed, int N, int h, int w, void* workspace, size_t workspace_bytes, const float* grad_scale,
+                         float* grad_pred, enerf_stream_t stream) {
+    REQUIRE(packed && workspace && grad_pred, "perceptual_bwd: null pointer");
+    REQUIRE(((size_t)workspace & 15) == 0 && ((size_t)packed & 15) == 0, "perceptual_bwd: packed and workspace must be 16-byte aligned");
+    const int rc = perceptual_check_shape("perceptual_bwd", N, h, w);
+    if (rc != ENERF_OK) return rc;
+    const size_t need = perceptual_workspace_bytes(N, h, w);
+    if (workspace_bytes < need) return fail(ENERF_EWORKSPACE, "perceptual_bwd: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    launch_perceptual_bwd(packed, N, h, w, workspace, grad_scale, grad_pred, (hipStream_t)stream);
+    return check_launch("perceptual_bwd");
+}
+long long enerf_vgg_conv3x3_dgrad_packed_floats(int cin, int cout) {
+    return vgg_dgrad_supported(cin, cout) ? vgg_dgrad_packed_floats(cin, cout) : 0;
+}
+int enerf_vgg_conv3x3_dgrad_pack(const float* w, int cin, int cout, float* packed, enerf_stream_t stream) {
+    REQUIRE(w && packed, "vgg_conv3x3_dgrad_pack: null pointer");
+    REQUIRE(vgg_dgrad_supported(cin, cout), "vgg_conv3x3_dgrad_pack: unsupported layer %d -> %d (not one of the ten trunk layers)", cin, cout);
+    launch_vgg_dgrad_pack(w, cin, cout, packed, (hipStream_t)stream);
+    return check_launch("vgg_conv3x3_dgrad_pack");
+}
+int enerf_vgg_conv3x3_dgrad(const float* packed, int cin, int cout, const float* gout_cl, float* gin_cl, int N, int H, int W,
+                            enerf_stream_t stream) {
+    REQUIRE(packed && gout_cl && gin_cl, "vgg_conv3x3_dgrad: null pointer");
+    REQUIRE(vgg_dgrad_supported(cin, cout), "vgg_conv3x3_dgrad: unsupported layer %d -> %d (not one of the ten trunk layers)", cin, cout);
+    REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W * (cin > cout ? cin : cout) < (1LL << 31) * 4,
+            "vgg_conv3x3_dgrad: bad shape (N %d, H %d, W %d)", N, H, W);
+    REQUIRE(((size_t)packed & 15) == 0 && ((size_t)gout_cl & 15) == 0 && (cin == 3 || ((size_t)gin_cl & 15) == 0),
+            "vgg_conv3x3_dgrad: packed, gout_cl and gin_cl must be 16-byte aligned");
+    launch_vgg_conv3x3_dgrad(packed, cin, cout, gout_cl, gin_cl, N, H, W, (hipStream_t)stream);
+    return check_launch("vgg_conv3x3_dgrad");
+}
 int enerf_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                       enerf_stream_t stream) {
     REQUIRE(tar_ext && tar_ixt && xy && rays && B > 0 && N >= 0 && scale > 0.f, "gen_rays_at: bad arguments");

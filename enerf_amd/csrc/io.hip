@@ -486,3 +486,5 @@ void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* ma
 
 // Evaluator LPIPS (evaluators/enerf.py:81-87, enerf_human.py:71-77): the VGG16 trunk and the taps
 #include "lpips_vgg.h"
+// Trainer's perceptual term (losses/vgg_perceptual_loss.py:21-37): the same trunk's first ten layers, forward and backward
+#include "perceptual_vgg.h"

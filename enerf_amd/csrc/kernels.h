@@ -241,6 +241,21 @@ void launch_lpips_pack(const enerf_lpips_raw_t& raw, float* packed, hipStream_t 
 size_t eval_lpips_workspace_bytes(int B, int rh, int rw);
 void launch_eval_lpips(const float* packed, const VggFront& front, int rh, int rw, void* workspace, double* out, hipStream_t st);
 void launch_mask_bbox(const void* mask, int mask_bytes, int mask_mode, int B, int img_h, int img_w, int* rect, hipStream_t st);
+// The trainer's perceptual term (perceptual_vgg.h, included by io.hip): the first ten trunk layers forward with every output kept,
+// L1 taps, and the ten data-gradient layers back into the rendered image.  (cin, cout) always name the FORWARD layer.
+long long perceptual_packed_floats();
+void launch_perceptual_pack(const enerf_perceptual_raw_t& raw, float* packed, hipStream_t st);
+size_t perceptual_workspace_bytes(int N, int h, int w);
+void perceptual_layout(int N, int h, int w, long long* offsets);
+void launch_perceptual_fwd(const float* packed, const float* pred, const float* gt, int N, int h, int w, void* workspace, double* out,
+                           hipStream_t st);
+void launch_perceptual_bwd(const float* packed, int N, int h, int w, void* workspace, const float* grad_scale, float* grad_pred,
+                           hipStream_t st);
+bool vgg_dgrad_supported(int cin, int cout);
+long long vgg_dgrad_packed_floats(int cin, int cout);
+void launch_vgg_dgrad_pack(const float* w, int cin, int cout, float* packed, hipStream_t st);
+void launch_vgg_conv3x3_dgrad(const float* packed_d, int cin, int cout, const float* gout, float* gin, int N, int H, int W,
+                              hipStream_t st);
 void launch_gen_rays_at(const float* tar_ext, const float* tar_ixt, const int* xy, int B, int N, float scale, float* rays,
                         hipStream_t st);
 void launch_rays_bbox_mask(const float* rays, const float* bounds, long long n, int* mask, hipStream_t st);

@@ -17,6 +17,7 @@
 // streamed per tap row from the packed image (k_conv2d_pack's order [tap][cin/4][cout/16][lane]), never held: the 512 -> 512
 // image is 9.4 MB.  The 2x2 max pool is taken while staging (four loads instead of one): no pooled tensor is ever written.
 // Pixel tiles that lie wholly outside the image are skipped (a wave-uniform test), so a 1x1 map costs one tile, not sixteen.
+// (The same kernel serves the trainer's perceptual term, perceptual_vgg.h: its MODE template parameter selects what is staged.)
 // Conv 0 (3 -> 64, channels padded to 4, one k-step per tap) stages the evaluator's (B, h*w, 3) images directly: mask
 // zeroing, rectangle offset, (x - 0.5) * 2 and the scaling layer on load — NOT folded into the bias: the zero padding comes
 // after the scaling layer, so the halo is staged as zeros of the SCALED image.
@@ -79,17 +80,75 @@ void launch_lpips_pack(const enerf_lpips_raw_t& raw, float* packed, hipStream_t 
                             packed + lpips_lin_offset(l));
 }
 
+// what k_vgg_conv3x3 stages (its MODE): the trunk's own input (the evaluator front when f.pred is set), the trainer's images
+// through the perceptual term's normalisation, or the masked / seeded / pool-routed gradient of a data-gradient layer
+// (perceptual_vgg.h); the arithmetic behind the staging is one and the same
+constexpr int kVggStageTrunk = 0, kVggStagePerceptual = 1, kVggStageDgrad = 2;
+struct VggDgradStage {
+    const float* act;       // (N, H, W, cin) the layer's saved forward output: ReLU mask (and pool arg-max); nullptr: `in` as it is
+    const float* act_gt;    // the same of the gt images on a tap layer (the seed sign(act - act_gt) * seed), else nullptr
+    float seed;             // 1 / (N * cin * H * W)
+    int route, gH, gW;      // route: `in` is (N, gH, gW, cin), the gradient of the 2x2 floor max pool of `act`
+};
 struct VggConvArgs {
-    const float* wpk;       // the layer's packed image (A operands | bias)
-    const float* in;        // (N, Hin, Win, cin) channels-last; unused by the evaluator front
+    const float* wpk;       // the layer's packed image (A operands | bias; no bias in MODE kVggStageDgrad)
+    const float* in;        // (N, Hin, Win, cin) channels-last; unused by the fronts
     float* out;             // (N, H, W, cout)
     int cin, cout, H, W, Hin, Win, pool, relu, tiles_x;
-    VggFront f;             // f.pred != nullptr: conv 0 reads the evaluator's images (n < f.B: pred, else gt)
+    VggFront f;             // f.pred != nullptr: conv 0 reads (B, h*w, 3) images (n < f.B: pred, else gt)
+    VggDgradStage d;
 };
 
+// the trainer's images (lib/train/losses/vgg_perceptual_loss.py:18-26): (v - mean) / std on load; a.f.pred / a.f.gt (B, H*W, 3)
+__device__ __forceinline__ float4 vgg_stage_perceptual(const VggConvArgs& a, int n, int gy, int gx) {
+    const float* src = n < a.f.B ? a.f.pred : a.f.gt;
+    const float* p = src + (((long long)(n < a.f.B ? n : n - a.f.B) * a.H + gy) * a.W + gx) * 3;
+    return make_float4((p[0] - 0.485f) / 0.229f, (p[1] - 0.456f) / 0.224f, (p[2] - 0.406f) / 0.225f, 0.f);
+}
+// MaxPool2d(2, 2) backward: position k = 2 * (y & 1) + (x & 1) keeps the gradient when it holds the FIRST maximum of its window in
+// row-major order (torch's return_indices rule)
+__device__ __forceinline__ bool vgg_pool_first_max(int k, float v0, float v1, float v2, float v3) {
+    int m = 0;
+    float best = v0;
+    if (v1 > best) { best = v1; m = 1; }
+    if (v2 > best) { best = v2; m = 2; }
+    if (v3 > best) { best = v3; m = 3; }
+    return m == k;
+}
+__device__ __forceinline__ float vgg_sign_seed(float x, float y, float seed) { return x > y ? seed : (x < y ? -seed : 0.f); }
+// the input of a data-gradient layer, four channels c .. c + 3 of pixel (gy, gx): the incoming gradient (routed through the pool's
+// arg-max when the forward pooled on load behind this layer), plus the L1 tap's seed, times the ReLU mask (act > 0)
+__device__ __forceinline__ float4 vgg_stage_dgrad(const VggConvArgs& a, int n, int gy, int gx, int c) {
+    const long long rowf = (long long)a.W * a.cin, off = ((long long)n * a.H + gy) * rowf + (long long)gx * a.cin + c;
+    if (a.d.act == nullptr) return *reinterpret_cast<const float4*>(a.in + off);
+    const float4 av = *reinterpret_cast<const float4*>(a.d.act + off);
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.in != nullptr) {
+        if (!a.d.route) {
+            g = *reinterpret_cast<const float4*>(a.in + off);
+        } else if ((gy >> 1) < a.d.gH && (gx >> 1) < a.d.gW) {           // rows / columns beyond the floor: 0
+            const int py = gy >> 1, px = gx >> 1, k = 2 * (gy & 1) + (gx & 1);
+            const float4 gi = *reinterpret_cast<const float4*>(a.in + (((long long)n * a.d.gH + py) * a.d.gW + px) * a.cin + c);
+            const float* p = a.d.act + ((long long)n * a.H + 2 * py) * rowf + (long long)(2 * px) * a.cin + c;
+            const float4 v0 = *reinterpret_cast<const float4*>(p), v1 = *reinterpret_cast<const float4*>(p + a.cin);
+            const float4 v2 = *reinterpret_cast<const float4*>(p + rowf), v3 = *reinterpret_cast<const float4*>(p + rowf + a.cin);
+            g = make_float4(vgg_pool_first_max(k, v0.x, v1.x, v2.x, v3.x) ? gi.x : 0.f, vgg_pool_first_max(k, v0.y, v1.y, v2.y, v3.y) ? gi.y : 0.f,
+                            vgg_pool_first_max(k, v0.z, v1.z, v2.z, v3.z) ? gi.z : 0.f, vgg_pool_first_max(k, v0.w, v1.w, v2.w, v3.w) ? gi.w : 0.f);
+        }
+    }
+    if (a.d.act_gt != nullptr) {
+        const float4 yv = *reinterpret_cast<const float4*>(a.d.act_gt + off);
+        g.x += vgg_sign_seed(av.x, yv.x, a.d.seed); g.y += vgg_sign_seed(av.y, yv.y, a.d.seed);
+        g.z += vgg_sign_seed(av.z, yv.z, a.d.seed); g.w += vgg_sign_seed(av.w, yv.w, a.d.seed);
+    }
+    return make_float4(av.x > 0.f ? g.x : 0.f, av.y > 0.f ? g.y : 0.f, av.z > 0.f ? g.z : 0.f, av.w > 0.f ? g.w : 0.f);
+}
+
 // one staged item: four channels of the input pixel (gy, gx) of image n (inside the image; the caller zero-fills the rest)
-template <int CB>
+template <int CB, int MODE>
 __device__ __forceinline__ float4 vgg_stage_load(const VggConvArgs& a, int n, int gy, int gx, int cb, int q) {
+    if (MODE == kVggStageDgrad) return vgg_stage_dgrad(a, n, gy, gx, cb * 16 + q * 4);
+    if (MODE == kVggStagePerceptual) return vgg_stage_perceptual(a, n, gy, gx);
     if (CB == 16) {
         const long long rowf = (long long)a.Win * a.cin;
         if (!a.pool) return *reinterpret_cast<const float4*>(a.in + ((long long)n * a.Hin + gy) * rowf + (long long)gx * a.cin + cb * 16 + q * 4);
@@ -115,8 +174,16 @@ __device__ __forceinline__ float4 vgg_stage_load(const VggConvArgs& a, int n, in
 }
 
 // CB: input channels per LDS pass: 16 (cin a multiple of 16) or 4 (the 3-channel first layer).  grid (pixel tiles, cout / 64, N)
-template <int CB>
-__global__ __launch_bounds__(256) void k_vgg_conv3x3(const VggConvArgs a) {
+// The data-gradient staging (up to six loads per item) pushes the register count one past 256; its instantiation alone is told to
+// stay at two waves per SIMD, like the trunk's (two blocks per CU: one stages while the other multiplies).  The trunk's own
+// instantiations are compiled exactly as before.
+#ifdef ENERF_EMU
+#define ENERF_VGG_WAVES(mode)
+#else
+#define ENERF_VGG_WAVES(mode) __attribute__((amdgpu_waves_per_eu((mode) == kVggStageDgrad ? 2 : 1)))
+#endif
+template <int CB, int MODE = kVggStageTrunk>
+__global__ __launch_bounds__(256) ENERF_VGG_WAVES(MODE) void k_vgg_conv3x3(const VggConvArgs a) {
     constexpr int CPL = CB / 4, QV = CB / 4, NIT = (kVggNPX * QV + 255) / 256;
     __shared__ float4 lds4[kVggNPX * QV];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
@@ -148,7 +215,7 @@ __global__ __launch_bounds__(256) void k_vgg_conv3x3(const VggConvArgs a) {
             const int px = ic / QV, q = ic - px * QV;
             const int ly = px / kVggIW, lx = px - ly * kVggIW, gy = oy0 - 1 + ly, gx = ox0 - 1 + lx;
             sv[it] = make_float4(0.f, 0.f, 0.f, 0.f);           // zero padding (of the scaled image for conv 0) and tile overhang
-            if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) sv[it] = vgg_stage_load<CB>(a, n, gy, gx, cb, q);
+            if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) sv[it] = vgg_stage_load<CB, MODE>(a, n, gy, gx, cb, q);
         }
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -198,7 +265,7 @@ __global__ __launch_bounds__(256) void k_vgg_conv3x3(const VggConvArgs a) {
             for (int rt = 0; rt < 4; ++rt) sum[c][rt] += acc[c][rt];
     }
 
-    // epilogue: bias, ReLU; lane (g, j) holds channels 64cog + 16rt + 4g .. + 3 of pixel j of each of its tiles
+    // epilogue: bias, ReLU (a data gradient has neither); lane (g, j) holds channels 64cog + 16rt + 4g .. + 3 of pixel j of each of its tiles
     const float* bias = a.wpk + 9LL * KS * RT * 64;
     const int ox = ox0 + 16 * wx + j;
 #pragma unroll
@@ -209,6 +276,10 @@ __global__ __launch_bounds__(256) void k_vgg_conv3x3(const VggConvArgs a) {
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) {
             const int co = cog * 64 + rt * 16 + 4 * g;
+            if (MODE == kVggStageDgrad) {
+                *reinterpret_cast<float4*>(op + co) = make_float4(sum[c][rt][0], sum[c][rt][1], sum[c][rt][2], sum[c][rt][3]);
+                continue;
+            }
             const float4 bq = *reinterpret_cast<const float4*>(bias + co);
             float4 v = make_float4(sum[c][rt][0] + bq.x, sum[c][rt][1] + bq.y, sum[c][rt][2] + bq.z, sum[c][rt][3] + bq.w);
             if (a.relu) v = make_float4(relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w));

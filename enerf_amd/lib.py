@@ -137,11 +137,17 @@ class LpipsRaw(C.Structure):
     _fields_ = [("conv", _ConvWB * 13), ("lin", _f * 5)]
 
 
+class PerceptualRaw(C.Structure):
+    """``enerf_perceptual_raw_t``."""
+    _fields_ = [("conv", _ConvWB * 10)]
+
+
 # the VGG16 trunk of LPIPS: (cin, cout) of features.{0,2,5,7,10,12,14,17,19,21,24,26,28}, the tap widths, the rect modes
 VGG_CONVS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
              (512, 512), (512, 512), (512, 512))
 LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
 RECT_NONE, RECT_CROP, RECT_XYWH = 0, 1, 3
+PERCEPTUAL_CONVS = VGG_CONVS[:10]          # features[:23]: the trainer's perceptual term stops after relu4_3
 
 
 def cascade_struct(cfg) -> Cascade:
@@ -262,6 +268,15 @@ _SIGNATURES = {
     "enerf_vgg_conv3x3_pack": (_i, [_f, _f, _i, _i, _f, _f]),
     "enerf_vgg_conv3x3": (_i, [_f, _i, _i, _f, _f, _i, _i, _i, _i, _f]),
     "enerf_mask_bbox": (_i, [C.c_void_p, _i, _i, _i, _i, _i, C.c_void_p, _f]),
+    "enerf_perceptual_packed_floats": (_ll, []),
+    "enerf_perceptual_pack": (_i, [C.POINTER(PerceptualRaw), _f, _f]),
+    "enerf_perceptual_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "enerf_perceptual_layout": (_i, [_i, _i, _i, C.POINTER(_ll)]),
+    "enerf_perceptual_fwd": (_i, [_f, _f, _f, _i, _i, _i, C.c_void_p, C.c_size_t, C.c_void_p, _f]),
+    "enerf_perceptual_bwd": (_i, [_f, _i, _i, _i, C.c_void_p, C.c_size_t, _f, _f, _f]),
+    "enerf_vgg_conv3x3_dgrad_packed_floats": (_ll, [_i, _i]),
+    "enerf_vgg_conv3x3_dgrad_pack": (_i, [_f, _i, _i, _f, _f]),
+    "enerf_vgg_conv3x3_dgrad": (_i, [_f, _i, _i, _f, _f, _i, _i, _i, _f]),
     "enerf_gen_rays_at": (_i, [_f, _f, C.c_void_p, _i, _i, _fl, _f, _f]),
     "enerf_rays_bbox_mask": (_i, [_f, _f, _ll, C.c_void_p, _f]),
     "enerf_select_views": (_i, [_f, _i, _f, _i, C.c_void_p, _f]),
@@ -1358,6 +1373,82 @@ class EnerfLib:
         out = torch.empty((N, H, W, cout), dtype=torch.float32, device=x_cl.device)
         self._check(self.dll.enerf_vgg_conv3x3(_ptr(packed_layer), int(cin), int(cout), _ptr(x_cl), _ptr(out), N, H, W, int(bool(relu)),
                                                self.stream_of(x_cl)), "vgg_conv3x3")
+        return out
+
+    # -- trainer's perceptual term (csrc/perceptual_vgg.h) ---------------------------------------------
+    def perceptual_pack(self, convs):
+        """``convs``: ten (w (cout,cin,3,3), b (cout)) pairs of VGG16 ``features[:23]`` in trunk order -> the packed image
+        ``perceptual_fwd`` / ``perceptual_bwd`` read (``enerf_amd.loss.PerceptualWeights`` builds the list)."""
+        if len(convs) != 10:
+            raise EnerfError("perceptual_pack needs 10 (w, b) pairs")
+        raw = PerceptualRaw()
+        for i, ((w, b), (cin, cout)) in enumerate(zip(convs, PERCEPTUAL_CONVS)):
+            if tuple(w.shape) != (cout, cin, 3, 3) or tuple(b.shape) != (cout,):
+                raise EnerfError(f"perceptual_pack: conv {i} must be ({cout},{cin},3,3) + ({cout},), got {tuple(w.shape)} + {tuple(b.shape)}")
+            raw.conv[i].w, raw.conv[i].b = _ptr(w), _ptr(b)
+        packed = torch.empty((self.dll.enerf_perceptual_packed_floats(),), dtype=torch.float32, device=convs[0][0].device)
+        self._check(self.dll.enerf_perceptual_pack(C.byref(raw), _ptr(packed), self.stream_of(packed)), "perceptual_pack")
+        return packed
+
+    def perceptual_workspace(self, N, h, w, device):
+        """A workspace for N image pairs of h x w (float32 tensor; its byte size is what the C entries are told)."""
+        nbytes = self.dll.enerf_perceptual_workspace_bytes(int(N), int(h), int(w))
+        if nbytes == 0:
+            raise EnerfError(f"perceptual loss failed: {self.dll.enerf_last_error().decode()}")
+        return torch.empty((nbytes // 4,), dtype=torch.float32, device=device)
+
+    def perceptual_layout(self, N, h, w):
+        """[(float offset, (2N, H_i, W_i, C_i))] of the ten saved activations in the workspace: pred images first, then gt."""
+        offs = (_ll * 10)()
+        self._check(self.dll.enerf_perceptual_layout(int(N), int(h), int(w), offs), "perceptual_layout")
+        out, H, W = [], int(h), int(w)
+        for i, (_, cout) in enumerate(PERCEPTUAL_CONVS):
+            if i in (2, 4, 7):
+                H, W = H // 2, W // 2
+            out.append((int(offs[i]), (2 * int(N), H, W, cout)))
+        return out
+
+    def perceptual_fwd(self, packed, pred_rgb, gt_rgb, image_hw, workspace=None):
+        """pred / gt (N, h*w, 3) -> (out, workspace): out 5 float64 on the device {loss, l_0 .. l_3} (no host read), the workspace
+        holding the ten saved activations ``perceptual_bwd`` needs."""
+        h, w = int(image_hw[0]), int(image_hw[1])
+        if h <= 0 or w <= 0 or pred_rgb.numel() == 0 or pred_rgb.numel() % (h * w * 3) or gt_rgb.numel() != pred_rgb.numel():
+            raise EnerfError(f"perceptual_fwd: pred / gt must be (N, {h}*{w}, 3) tensors of the same size")
+        N = pred_rgb.numel() // (h * w * 3)
+        ws = workspace if workspace is not None else self.perceptual_workspace(N, h, w, pred_rgb.device)
+        out = torch.empty((5,), dtype=torch.float64, device=pred_rgb.device)
+        self._check(self.dll.enerf_perceptual_fwd(_ptr(packed), _ptr(pred_rgb), _ptr(gt_rgb), N, h, w, ws.data_ptr(), ws.numel() * 4,
+                                                  out.data_ptr(), self.stream_of(pred_rgb)), "perceptual_fwd")
+        return out, ws
+
+    def perceptual_bwd(self, packed, N, image_hw, workspace, grad_scale=None):
+        """d loss / d pred (N, h*w, 3) from the workspace ``perceptual_fwd`` left; ``grad_scale``: a float32 device scalar or None."""
+        h, w = int(image_hw[0]), int(image_hw[1])
+        if grad_scale is not None and grad_scale.numel() != 1:
+            raise EnerfError("perceptual_bwd: grad_scale must hold one float")
+        grad = torch.empty((int(N), h * w, 3), dtype=torch.float32, device=workspace.device)
+        self._check(self.dll.enerf_perceptual_bwd(_ptr(packed), int(N), h, w, workspace.data_ptr(), workspace.numel() * 4,
+                                                  _ptr(grad_scale), _ptr(grad), self.stream_of(workspace)), "perceptual_bwd")
+        return grad
+
+    def vgg_conv3x3_dgrad_pack(self, w):
+        """w (cout,cin,3,3) of one of the ten trunk layers -> the packed image of its data gradient."""
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        n = self.dll.enerf_vgg_conv3x3_dgrad_packed_floats(cin, cout)
+        if n == 0 or tuple(w.shape[2:]) != (3, 3):
+            raise EnerfError(f"vgg_conv3x3_dgrad_pack: unsupported layer {tuple(w.shape)} (not one of the ten trunk layers)")
+        packed = torch.empty((n,), dtype=torch.float32, device=w.device)
+        self._check(self.dll.enerf_vgg_conv3x3_dgrad_pack(_ptr(w), cin, cout, _ptr(packed), self.stream_of(w)), "vgg_conv3x3_dgrad_pack")
+        return packed
+
+    def vgg_conv3x3_dgrad(self, packed, cin, cout, gout_cl):
+        """The gradient of one trunk layer (cin -> cout) with respect to its input, plain: gout_cl (N,H,W,cout) -> (N,H,W,cin)."""
+        if gout_cl.dim() != 4 or gout_cl.shape[3] != cout:
+            raise EnerfError(f"vgg_conv3x3_dgrad: gradient must be (N,H,W,{cout}) channels-last, got {tuple(gout_cl.shape)}")
+        N, H, W, _ = gout_cl.shape
+        out = torch.empty((N, H, W, cin), dtype=torch.float32, device=gout_cl.device)
+        self._check(self.dll.enerf_vgg_conv3x3_dgrad(_ptr(packed), int(cin), int(cout), _ptr(gout_cl), _ptr(out), N, H, W,
+                                                     self.stream_of(gout_cl)), "vgg_conv3x3_dgrad")
         return out
 
     def mask_bbox(self, mask, image_hw, mask_is_one=False, sync=True):

@@ -694,6 +694,48 @@ int enerf_vgg_conv3x3(const float* packed_layer, int cin, int cout, const float*
                       int relu, enerf_stream_t stream);
 int enerf_mask_bbox(const void* mask, int elem_bytes, int mask_mode, int B, int h, int w, int* rect, enerf_stream_t stream);
 
+/* ---- trainer's perceptual term on the device (ABI v11 grew by these entries; new symbols only, the version number is unchanged) ----
+ * VGGPerceptualLoss of lib/train/losses/vgg_perceptual_loss.py:21-37 as losses/enerf.py:30-51 calls it (resize=False,
+ * feature_layers=[0,1,2,3], no style layers), forward AND backward: x = (img - mean) / std (ImageNet), torchvision VGG16
+ * features[:23] (ten 3x3 convs with bias + ReLU, a 2x2 floor max pool in front of convs 2, 4, 7),
+ * loss = sum_l mean|x_l - y_l| after relu1_2, relu2_2, relu3_3, relu4_3, each mean over all N*C*H*W elements.  The convolutions are
+ * the evaluator LPIPS's exact-fp32 MFMA kernel; the backward pass is ten data-gradient launches (the weights are frozen) that
+ * apply the ReLU mask, the taps' seeds sign(x - y) / count and the max pools' arg-max routing (first maximum in row-major order,
+ * torch's rule) while staging.  No weights ship: the caller packs their own.
+ *   enerf_perceptual_raw_t            torch-layout device pointers {w (cout,cin,3,3), b (cout)} of features.{0,2,5,7,10,12,14,17,19,21}
+ *   enerf_perceptual_packed_floats    floats of the packed image; enerf_perceptual_pack builds it (per forward layer A operands |
+ *                                     bias, then the ten data-gradient images)
+ *   enerf_perceptual_workspace_bytes  bytes for N image pairs of h x w (0: refused, see enerf_last_error): 4 x 1024 float64 tap
+ *                                     partials | the ten saved activations | two ping-pong gradient buffers.  16-byte aligned.
+ *   enerf_perceptual_layout           offsets[i]: float offset from the workspace's start of saved activation i, (2N, H_i, W_i, C_i)
+ *                                     channels-last, the N pred images first, then the N gt images; C = 64,64,128,128,256,256,256,
+ *                                     512,512,512; H_i, W_i: h, w halved (floor) in front of i = 2, 4, 7.
+ *   enerf_perceptual_fwd              pred / gt (N, h*w, 3) -> out, 5 doubles {loss, l_0 .. l_3}, loss = ((l_0 + l_1) + l_2) + l_3.
+ *                                     Bit-identical from call to call (no floating-point atomics); pred == gt gives exactly 0.
+ *   enerf_perceptual_bwd              reads only `packed` and the workspace enerf_perceptual_fwd left: grad_pred (N, h*w, 3) =
+ *                                     d loss / d pred, times *grad_scale when that DEVICE scalar is given (NULL = 1; no host read:
+ *                                     an autograd backward stays graph-capturable).  Bit-identical from call to call.
+ *   Both only enqueue.  h < 8 or w < 8 (relu4_3 would be empty), null pointers, N outside 1..32767 or tensors past the element
+ *   limit of the other entries: ENERF_EINVAL before anything is launched; a workspace that is too small: ENERF_EWORKSPACE.
+ *   enerf_vgg_conv3x3_dgrad           one data-gradient layer alone, plain (no mask, no seed, no pool): (cin, cout) name the FORWARD
+ *                                     layer, one of the ten above; gout_cl (N,H,W,cout) -> gin_cl (N,H,W,cin) = conv_transpose2d(gout,
+ *                                     w, padding=1).  packed: enerf_vgg_conv3x3_dgrad_pack of w (cout,cin,3,3). */
+typedef struct {
+    struct { const float *w, *b; } conv[10];
+} enerf_perceptual_raw_t;
+long long enerf_perceptual_packed_floats(void);
+int enerf_perceptual_pack(const enerf_perceptual_raw_t* raw, float* packed, enerf_stream_t stream);
+size_t enerf_perceptual_workspace_bytes(int N, int h, int w);
+int enerf_perceptual_layout(int N, int h, int w, long long* offsets);
+int enerf_perceptual_fwd(const float* packed, const float* pred_rgb, const float* gt_rgb, int N, int h, int w, void* workspace,
+                         size_t workspace_bytes, double* out, enerf_stream_t stream);
+int enerf_perceptual_bwd(const float* packed, int N, int h, int w, void* workspace, size_t workspace_bytes, const float* grad_scale,
+                         float* grad_pred, enerf_stream_t stream);
+long long enerf_vgg_conv3x3_dgrad_packed_floats(int cin, int cout);
+int enerf_vgg_conv3x3_dgrad_pack(const float* w, int cin, int cout, float* packed, enerf_stream_t stream);
+int enerf_vgg_conv3x3_dgrad(const float* packed, int cin, int cout, const float* gout_cl, float* gin_cl, int N, int H, int W,
+                            enerf_stream_t stream);
+
 /* ---- source-view cache (ABI v11 grew by these five entries; new symbols only, the version number is unchanged) ----
  * A static scene (dtu / llff / nerf test splits) or one time frame of the interactive viewer draws the S source views of every
  * frame from one fixed set of V images: zjumocap/enerf_interactive.py:102-105,138-153 (cache_data) preloads the V views once and
