@@ -127,9 +127,10 @@ def feature_volume(feats_level, proj, dv):
     """homo_warp for every view at once + biased variance (utils.py:57-95, 322-349): feats (B,S,C,Hs,Ws) -> (B,C,D,h,w)."""
     B, S, C, Hs, Ws = feats_level.shape
     _, D, h, w = dv.shape
-    dev = dv.device
-    ys, xs = torch.meshgrid(torch.linspace(0, h - 1, h, device=dev), torch.linspace(0, w - 1, w, device=dev), indexing="ij")
-    g = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(h * w, device=dev)], 0)          # (3, hw)
+    dev, dt = dv.device, dv.dtype
+    ys, xs = torch.meshgrid(torch.linspace(0, h - 1, h, device=dev, dtype=dt), torch.linspace(0, w - 1, w, device=dev, dtype=dt),
+                            indexing="ij")
+    g = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(h * w, device=dev, dtype=dt)], 0)          # (3, hw)
     R, T = proj[..., :3], proj[..., 3:]                                                          # (B,S,3,3), (B,S,3,1)
     rot = (R @ g).unsqueeze(3)                                                                   # (B,S,3,1,hw)
     p = rot + T.unsqueeze(-1) / dv.reshape(B, 1, 1, D, h * w)                                    # (B,S,3,D,hw)
