@@ -750,4 +750,20 @@ int enerf_gather_views(const float* inps, const float* exts, const float* ixts, 
     launch_gather_views(inps, exts, ixts, idx, k, H, W, src_inps, src_exts, src_ixts, (hipStream_t)stream);
     return check_launch("gather_views");
 }
+int enerf_ingest_views_u8(const unsigned char* img, const unsigned char* mask, int dilate, int V, int H, int W, float* out,
+                          enerf_stream_t stream) {
+    REQUIRE(dilate == 0 || (dilate % 2 == 1 && dilate >= 3 && dilate <= 9), "ingest_views_u8: dilate=%d (0, or an odd box size 3..9)", dilate);
+    REQUIRE(V >= 1 && V <= 65535, "ingest_views_u8: V=%d views (1..65535)", V);
+    REQUIRE(H >= 1 && W >= 1 && H <= 16 * 65535, "ingest_views_u8: bad image extent %dx%d", H, W);
+    REQUIRE(img && out, "ingest_views_u8: null %s", img ? "out" : "img");
+    launch_ingest_views_u8(img, mask, dilate, V, H, W, out, (hipStream_t)stream);
+    return check_launch("ingest_views_u8");
+}
+int enerf_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
+                          enerf_stream_t stream) {
+    REQUIRE(vertices && tar_ext && near_far, "bounds_near_far: null pointer");
+    REQUIRE(B >= 1 && n >= 1, "bounds_near_far: B=%d cameras, n=%d vertices (both >= 1)", B, n);
+    launch_bounds_near_far(vertices, n, tar_ext, B, near_min, near_far, (hipStream_t)stream);
+    return check_launch("bounds_near_far");
+}
 }  // extern "C"

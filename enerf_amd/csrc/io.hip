@@ -198,6 +198,144 @@ void launch_gather_views(const float* inps, const float* exts, const float* ixts
 }
 
 // -------------------------------------------------------------------------------------------------
+// The time frame's images as the camera / decoder delivers them (zjumocap/enerf_interactive.py:116-124,135 read_data and :145
+// cache_data, for an undistorted image at input_ratio 1): img (V,H,W,3) uint8 + mask (V,H,W) uint8 -> out (V,3,H,W) float32,
+//   keep = dilate(mask != 0, box of `dilate`^2 ones, pixels outside the image do not count);  x = u8 / 255;  x[!keep] = 0;  2x - 1
+// so a masked-out pixel is -1.  Bit-exact: the division is the correctly rounded one (no reciprocal), 2x is exact and 2x - 1 rounds
+// once whether or not it is contracted into an fma.
+//
+// Memory-bound (4 bytes read, 12 written per pixel).  A 256-thread block takes a tile of 256 x 16 pixels; a lane owns four
+// consecutive pixels of a row, a wave one row of the tile, four passes.  Fast path (W % 4 == 0 and aligned pointers): the lane's 12
+// image bytes are three dword loads, every plane gets one float4 store.  Otherwise the same lane walks its four pixels bytewise with
+// the row's end checked per pixel.  The dilation is separable: the tile of `keep` bytes with its halo (at most 24 x 264) is staged in
+// LDS once, a horizontal pass ORs 2r + 1 neighbours per byte, and the vertical pass ORs 2r + 1 DWORDS — four pixels at a time —
+// in registers.  24 x 264 + 24 x 256 bytes of LDS per block.
+// -------------------------------------------------------------------------------------------------
+constexpr int kIngTW = 256, kIngTH = 16, kIngR = 4;                       // tile; widest halo (dilate 9)
+constexpr int kIngRows = kIngTH + 2 * kIngR, kIngPitch = kIngTW + 2 * kIngR;
+
+__device__ __forceinline__ float ingest_value(unsigned u, bool keep) {
+    float x = (float)u / 255.f;                                           // IEEE division: what `u8.float() / 255` is
+    x = keep ? x : 0.f;
+    return 2.f * x - 1.f;
+}
+__global__ __launch_bounds__(256) void k_ingest_views_u8(const unsigned char* __restrict__ img,
+                                                         const unsigned char* __restrict__ mask, int r, int H, int W, int fast,
+                                                         float* __restrict__ out) {
+    __shared__ unsigned s_raw[kIngRows * kIngPitch / 4];                  // keep bytes of the tile + halo
+    __shared__ unsigned s_hor[kIngRows * kIngTW / 4];                     // after the horizontal pass (no horizontal halo left)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tx0 = blockIdx.x * kIngTW, ty0 = blockIdx.y * kIngTH;
+    const long long hw = (long long)H * W;
+    const unsigned char* im = img + (long long)blockIdx.z * hw * 3;
+    const unsigned char* mk = mask != nullptr ? mask + (long long)blockIdx.z * hw : nullptr;
+    float* o = out + (long long)blockIdx.z * hw * 3;
+    const bool dil = mk != nullptr && r > 0;                              // block-uniform
+    if (dil) {
+        unsigned char* raw = reinterpret_cast<unsigned char*>(s_raw);
+        unsigned char* hor = reinterpret_cast<unsigned char*>(s_hor);
+        const int rows = kIngTH + 2 * r, cols = kIngTW + 2 * r;
+        for (int ry = wave; ry < rows; ry += 4) {
+            const int y = ty0 - r + ry;
+            for (int rx = lane; rx < cols; rx += 64) {
+                const int x = tx0 - r + rx;
+                unsigned char k = 0;
+                if (y >= 0 && y < H && x >= 0 && x < W) k = mk[(long long)y * W + x] != 0 ? 1 : 0;
+                raw[ry * kIngPitch + rx] = k;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < rows * kIngTW; e += 256) {
+            const int ry = e / kIngTW, x = e - ry * kIngTW;
+            unsigned k = 0;
+            for (int t = 0; t <= 2 * r; ++t) k |= raw[ry * kIngPitch + x + t];
+            hor[e] = (unsigned char)k;
+        }
+        __syncthreads();
+    }
+    const int x = tx0 + lane * 4;
+    for (int pass = 0; pass < kIngTH / 4; ++pass) {
+        const int ly = pass * 4 + wave, y = ty0 + ly;
+        if (y >= H || x >= W) continue;
+        const long long p = (long long)y * W + x;
+        unsigned keep4 = 0x01010101u;                                     // one byte per pixel, != 0 = keep
+        if (dil) {
+            keep4 = 0;
+            for (int t = 0; t <= 2 * r; ++t) keep4 |= s_hor[(ly + t) * (kIngTW / 4) + lane];
+        } else if (mk != nullptr) {
+            if (fast) {
+                keep4 = *reinterpret_cast<const unsigned*>(mk + p);
+            } else {
+                keep4 = 0;
+                for (int q = 0; q < 4; ++q)
+                    if (x + q < W) keep4 |= (unsigned)mk[p + q] << (8 * q);
+            }
+        }
+        if (fast) {                                                       // W % 4 == 0: the four pixels exist, 12 aligned bytes
+            const unsigned* s = reinterpret_cast<const unsigned*>(im + p * 3);
+            const unsigned w0 = s[0], w1 = s[1], w2 = s[2];
+            const bool k0 = (keep4 & 0xffu) != 0, k1 = (keep4 & 0xff00u) != 0, k2 = (keep4 & 0xff0000u) != 0, k3 = (keep4 >> 24) != 0;
+            // bytes: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+            const float4 cr = make_float4(ingest_value(w0 & 255u, k0), ingest_value(w0 >> 24, k1),
+                                          ingest_value((w1 >> 16) & 255u, k2), ingest_value((w2 >> 8) & 255u, k3));
+            const float4 cg = make_float4(ingest_value((w0 >> 8) & 255u, k0), ingest_value(w1 & 255u, k1),
+                                          ingest_value(w1 >> 24, k2), ingest_value((w2 >> 16) & 255u, k3));
+            const float4 cb = make_float4(ingest_value((w0 >> 16) & 255u, k0), ingest_value((w1 >> 8) & 255u, k1),
+                                          ingest_value(w2 & 255u, k2), ingest_value(w2 >> 24, k3));
+            *reinterpret_cast<float4*>(o + p) = cr;
+            *reinterpret_cast<float4*>(o + hw + p) = cg;
+            *reinterpret_cast<float4*>(o + 2 * hw + p) = cb;
+        } else {
+            for (int q = 0; q < 4; ++q) {
+                if (x + q >= W) break;
+                const bool k = ((keep4 >> (8 * q)) & 255u) != 0;
+                const unsigned char* s = im + (p + q) * 3;
+                o[p + q] = ingest_value(s[0], k);
+                o[hw + p + q] = ingest_value(s[1], k);
+                o[2 * hw + p + q] = ingest_value(s[2], k);
+            }
+        }
+    }
+}
+void launch_ingest_views_u8(const unsigned char* img, const unsigned char* mask, int dilate, int V, int H, int W, float* out,
+                            hipStream_t st) {
+    const int fast = W % 4 == 0 && ((size_t)img & 3) == 0 && ((size_t)mask & 3) == 0 && ((size_t)out & 15) == 0;
+    ENERF_LAUNCH(k_ingest_views_u8, dim3((unsigned)cdiv(W, kIngTW), (unsigned)cdiv(H, kIngTH), (unsigned)V), 256, 0, st, img, mask,
+                 dilate / 2, H, W, fast, out);
+}
+
+// -------------------------------------------------------------------------------------------------
+// near_far of the interactive dataset's convert_data (zjumocap/enerf_interactive.py:198-201; zjumocap/enerf.py:163 with 0.1):
+//   z = vertices @ ext[:3,:3].T + ext[:3,3];  near_far = [max(min z, near_min), max z]
+// vertices (B,n,3), tar_ext (B,4,4) -> near_far (B,2), without the two .item() round trips.  One wave per batch element.
+// -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_bounds_near_far(const float* __restrict__ vertices, int n, const float* __restrict__ tar_ext,
+                                                        float near_min, float* __restrict__ near_far) {
+    const int b = blockIdx.x;
+    const float* e = tar_ext + b * 16;
+    const float r0 = e[8], r1 = e[9], r2 = e[10], t = e[11];
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const float* p = vertices + ((long long)b * n + i) * 3;
+        const float z = add_rn(add_rn(add_rn(mul_rn(p[0], r0), mul_rn(p[1], r1)), mul_rn(p[2], r2)), t);
+        lo = fminf(lo, z);
+        hi = fmaxf(hi, z);
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, m));
+        hi = fmaxf(hi, __shfl_xor(hi, m));
+    }
+    if (threadIdx.x == 0) {
+        near_far[2 * b] = fmaxf(lo, near_min);
+        near_far[2 * b + 1] = hi;
+    }
+}
+void launch_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
+                            hipStream_t st) {
+    ENERF_LAUNCH(k_bounds_near_far, (unsigned)B, 64, 0, st, vertices, n, tar_ext, near_min, near_far);
+}
+
+// -------------------------------------------------------------------------------------------------
 // gui_human.py:88-91:  img *= 255; img.to(uint8); flip(0)   — rgb (H*W,3) float -> (H,W,3) uint8
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pack_rgb8(const float* __restrict__ rgb, int H, int W, int flip,

@@ -262,6 +262,10 @@ void launch_rays_bbox_mask(const float* rays, const float* bounds, long long n, 
 void launch_select_views(const float* cam_points, int V, const float* c2w, int k, int* idx, hipStream_t st);
 void launch_gather_views(const float* inps, const float* exts, const float* ixts, const int* idx, int k, int H, int W,
                          float* src_inps, float* src_exts, float* src_ixts, hipStream_t st);
+void launch_ingest_views_u8(const unsigned char* img, const unsigned char* mask, int dilate, int V, int H, int W, float* out,
+                            hipStream_t st);
+void launch_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
+                            hipStream_t st);
 
 // ---- frame.hip (mask_at_box compaction; the frame driver — FrameRun's stages, run_frame — and its side lane, side_lane.h, live there too) ----
 size_t mask_compact_workspace_bytes(long long n);

@@ -287,6 +287,8 @@ _SIGNATURES = {
                                       C.POINTER(Options), _f]),
     "enerf_forward_cached_workspace_bytes": (C.c_size_t, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct)]),
     "enerf_forward_cached": (_i, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct), C.c_void_p, _f]),
+    "enerf_ingest_views_u8": (_i, [C.c_void_p, C.c_void_p, _i, _i, _i, _i, _f, _f]),
+    "enerf_bounds_near_far": (_i, [_f, _i, _f, _i, _fl, _f, _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1155,10 +1157,15 @@ class EnerfLib:
         self._check(self.dll.enerf_source_cache_sizes(C.byref(cas), V, H, W, C.byref(l2s), floats), "source_cache_sizes")
         return l2s.value, list(floats)
 
-    def source_cache_build(self, cache: "SourceCacheStruct", src_inps, exts, ixts, packed, cas: "Cascade", chunk=0, options=None):
+    def source_cache_build_workspace(self, H: int, W: int, device):
+        """The build's scratch (the FeatureNet workspace of 4 images): a caller that rebuilds keeps one and passes it back in."""
+        nb = self.dll.enerf_source_cache_build_workspace_bytes(H, W)
+        return torch.empty(((nb + 3) // 4,), dtype=torch.float32, device=device)
+
+    def source_cache_build(self, cache: "SourceCacheStruct", src_inps, exts, ixts, packed, cas: "Cascade", chunk=0, options=None,
+                           workspace=None):
         """FeatureNet + texel packing of ``src_inps`` (V,3,H,W) into the cache's buffers, ``chunk`` (<= 4) images at a time."""
-        nb = self.dll.enerf_source_cache_build_workspace_bytes(cache.H, cache.W)
-        ws = torch.empty(((nb + 3) // 4,), dtype=torch.float32, device=src_inps.device)
+        ws = workspace if workspace is not None else self.source_cache_build_workspace(cache.H, cache.W, src_inps.device)
         self._check(self.dll.enerf_source_cache_build(C.byref(cache), _ptr(src_inps), _ptr(exts), _ptr(ixts), _ptr(packed),
                                                       C.byref(cas), int(chunk), ws.data_ptr(), ws.numel() * 4, _opt(options),
                                                       self.stream_of(src_inps)), "source_cache_build")
@@ -1224,6 +1231,41 @@ class EnerfLib:
         self._check(self.dll.enerf_gather_views(_ptr(inps), _ptr(exts), _ptr(ixts), idx.data_ptr(), k, H, W, _ptr(si),
                                                 _ptr(se), _ptr(sk), self.stream_of(inps)), "gather_views")
         return si, se, sk
+
+    def ingest_views_u8(self, img, mask=None, dilate=0, out=None):
+        """zjumocap/enerf_interactive.py:116-124,135 + :145 on the device: img (V,H,W,3) uint8, mask (V,H,W) uint8 / bool or None
+        -> (V,3,H,W) float32 in [-1,1], masked-out pixels (after a ``dilate`` x ``dilate`` box dilation of ``mask != 0``) at -1."""
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3 or not img.is_contiguous():
+            raise EnerfError(f"ingest_views_u8: img must be a contiguous uint8 (V,H,W,3) tensor, got {img.dtype} {tuple(img.shape)}")
+        V, H, W, _ = img.shape
+        if mask is not None:
+            if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (V, H, W) or not mask.is_contiguous() \
+                    or mask.device != img.device:
+                raise EnerfError(f"ingest_views_u8: mask must be a contiguous uint8 / bool ({V},{H},{W}) tensor on the image's device")
+        if out is None:
+            out = torch.empty((V, 3, H, W), dtype=torch.float32, device=img.device)
+        elif tuple(out.shape) != (V, 3, H, W) or out.device != img.device:
+            raise EnerfError(f"ingest_views_u8: out must be ({V},3,{H},{W}) on the image's device")
+        self._check(self.dll.enerf_ingest_views_u8(img.data_ptr(), None if mask is None else mask.data_ptr(), int(dilate), V, H, W,
+                                                   _ptr(out), self.stream_of(img)),
+                    "ingest_views_u8")
+        return out
+
+    def bounds_near_far(self, vertices, tar_ext, near_min=0.05):
+        """zjumocap/enerf_interactive.py:198-201 without its two ``.item()``: vertices (n,3) or (B,n,3), tar_ext (B,4,4) ->
+        near_far (B,2) = [max(min z, near_min), max z] of the vertices' camera-space depths."""
+        B = tar_ext.shape[0]
+        if tuple(tar_ext.shape) != (B, 4, 4) or vertices.shape[-1] != 3 or vertices.dim() not in (2, 3):
+            raise EnerfError(f"bounds_near_far: vertices (n,3) / (B,n,3) and tar_ext (B,4,4), got {tuple(vertices.shape)} / {tuple(tar_ext.shape)}")
+        if vertices.dim() == 2:
+            vertices = vertices[None].expand(B, -1, -1)
+        if vertices.shape[0] != B:
+            raise EnerfError(f"bounds_near_far: {vertices.shape[0]} vertex sets for {B} cameras")
+        vertices = vertices.contiguous()
+        near_far = torch.empty((B, 2), dtype=torch.float32, device=tar_ext.device)
+        self._check(self.dll.enerf_bounds_near_far(_ptr(vertices), vertices.shape[1], _ptr(tar_ext), B, float(near_min),
+                                                   _ptr(near_far), self.stream_of(tar_ext)), "bounds_near_far")
+        return near_far
 
     def eval_stats(self, pred_rgb, gt_rgb, mask=None, pred_depth=None, gt_depth=None, image_hw=None, crop=(0, 0),
                    sync=True):

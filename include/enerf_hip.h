@@ -779,6 +779,25 @@ size_t enerf_forward_cached_workspace_bytes(const enerf_frame_args_t* args, cons
 int enerf_forward_cached(const enerf_frame_args_t* args, const enerf_source_cache_t* cache, const int* view_idx,
                          enerf_stream_t stream);
 
+/* ---- time frames of a dynamic scene (ABI v11 grew by these two entries; new symbols only, the version number is unchanged) ----
+ * What the interactive dataset does on the host for every time frame and every target camera, as device entries, so that a
+ * sequence can be streamed as uint8 (4 bytes per pixel instead of 12) and prepared without a readback.
+ *   enerf_ingest_views_u8   replaces read_data + cache_data, zjumocap/enerf_interactive.py:116-124,135 and :145 (for an undistorted
+ *       image at input_ratio 1): img (V,H,W,3) uint8, mask (V,H,W) uint8 or NULL (= keep everything) -> out (V,3,H,W) float32,
+ *       enerf_source_cache_build's input.  keep = mask != 0, dilated by a dilate x dilate box of ones anchored at its centre
+ *       (cv2.dilate's default border: pixels outside the image do not count; == max_pool2d(keep, dilate, 1, dilate / 2));
+ *       x = (float)u8 / 255.f (correctly rounded), x = 0 where !keep, out = 2x - 1: a masked-out pixel is -1.  Bit-exact to the
+ *       float32 expression for all 256 values.  dilate: 0 (none) or an odd box size 3..9.  Any H, W >= 1; rows whose 3*W bytes are
+ *       not dword-aligned (or unaligned pointers) take a bytewise path with identical results.  ENERF_EINVAL, nothing launched:
+ *       even dilate, dilate > 9, V < 1, NULL img or out.
+ *   enerf_bounds_near_far   replaces convert_data's :198-201 (two .item() host syncs per camera): vertices (B,n,3), tar_ext (B,4,4)
+ *       -> near_far (B,2) = [max(min z, near_min), max z], z = vertices @ ext[:3,:3].T + ext[:3,3] in fp32.  near_min is 0.05 in
+ *       the interactive dataset, 0.1 in zjumocap/enerf.py:163. */
+int enerf_ingest_views_u8(const unsigned char* img, const unsigned char* mask, int dilate, int V, int H, int W, float* out,
+                          enerf_stream_t stream);
+int enerf_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
+                          enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
