@@ -1,6 +1,7 @@
 // capi.hip — the extern "C" boundary (include/enerf_hip.h): argument validation, the cost-regularisation
 // network driver, error reporting.  No torch types; raw device pointers + sizes + a hipStream_t.
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "kernels.h"
@@ -354,6 +355,89 @@ int enerf_render_rays(const enerf_render_args_t* a, enerf_stream_t stream) {
         return fail(ENERF_EINVAL, "render_rays: unsupported configuration (code %d: F=%d S=%d n_samples=%d B=%d)", rc,
                     a->F, a->S, a->n_samples, a->B);
     return check_launch("render_rays");
+}
+
+
+// ---- the composite network's entries (include/enerf_hip.h) ----
+static int check_window(const char* what, int h, int w, int x0, int y0, int ww, int wh) {
+    REQUIRE(h > 0 && w > 0 && ww > 0 && wh > 0 && x0 >= 0 && y0 >= 0 && (long long)x0 + ww <= w && (long long)y0 + wh <= h,
+            "%s: window (x0 %d, y0 %d, %d x %d) outside the %d x %d grid", what, x0, y0, ww, wh, w, h);
+    return ENERF_OK;
+}
+int enerf_build_feature_volume_window(const float* feat, const float* proj, const float* depth_values, int B, int S, int C, int Hs,
+                                      int Ws, int D, int h, int w, int x0, int y0, int ww, int wh, float* vol, enerf_stream_t stream) {
+    REQUIRE(feat && proj && depth_values && vol, "build_feature_volume_window: null pointer");
+    REQUIRE(C == 16 || C == 32, "build_feature_volume_window: C=%d unsupported (16/32)", C);
+    REQUIRE(B > 0 && S > 0 && Hs > 1 && Ws > 1 && D > 0, "build_feature_volume_window: bad shape");
+    if (int rc = check_window("build_feature_volume_window", h, w, x0, y0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "build_feature_volume_window: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww, D);
+    REQUIRE((long long)B * S * Hs * Ws * C < (1LL << 32) && (long long)Hs * Ws < (1LL << 23),
+            "build_feature_volume_window: source features too large for 32-bit gather offsets");
+    REQUIRE((long long)B * D * h * w * (C / 4) < (1LL << 31) && (long long)h * w < (1LL << 23),
+            "build_feature_volume_window: grid too large for 32-bit voxel indices");
+    REQUIRE((long long)B * D <= 65535 * 2 && (long long)B * D * h < (1LL << 23) && w < (1 << 23),
+            "build_feature_volume_window: B*D=%lld planes / B*D*h=%lld rows beyond the grid-carried voxel decomposition",
+            (long long)B * D, (long long)B * D * h);
+    launch_feature_volume_window(feat, proj, depth_values, B, S, C, Hs, Ws, D, h, w, x0, y0, ww, wh, vol, (hipStream_t)stream);
+    return check_launch("build_feature_volume_window");
+}
+int enerf_depth_regression_window(const float* prob, const float* depth_values, int B, int D, int h, int w, int x0, int y0, int ww,
+                                  int wh, int depth_inv, float* depth, float* std, enerf_stream_t stream) {
+    REQUIRE(prob && depth_values && depth && std, "depth_regression_window: null pointer");
+    REQUIRE(B > 0 && D > 0 && D <= 64, "depth_regression_window: B=%d, D=%d unsupported (D in 1..64)", B, D);
+    if (int rc = check_window("depth_regression_window", h, w, x0, y0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "depth_regression_window: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww, D);
+    REQUIRE((long long)B * D * h * w < (1LL << 31), "depth_regression_window: grid too large");
+    launch_depth_regression_window(prob, depth_values, B, D, h, w, x0, y0, ww, wh, depth_inv, depth, std, (hipStream_t)stream);
+    return check_launch("depth_regression_window");
+}
+int enerf_window_ray_index(int x0, int y0, int ww, int wh, int Hr, int Wr, int* index, int* count, enerf_stream_t stream) {
+    REQUIRE(index && count, "window_ray_index: null pointer");
+    if (int rc = check_window("window_ray_index", Hr, Wr, x0, y0, ww, wh)) return rc;
+    REQUIRE((long long)Hr * Wr < (1LL << 31), "window_ray_index: ray raster too large");
+    launch_window_ray_index(x0, y0, ww, wh, Wr, index, count, (hipStream_t)stream);
+    return check_launch("window_ray_index");
+}
+int enerf_render_rays_raw(const enerf_render_raw_args_t* a, enerf_stream_t stream) {
+    REQUIRE(a, "render_rays_raw: null args");
+    if (a->N == 0 && a->B > 0) return ENERF_OK;
+    REQUIRE((a->rays12 || a->rays8) && a->tex && a->src_exts && a->src_ixts && a->tar_ext && a->packed && a->raw && a->z,
+            "render_rays_raw: null pointer");
+    if (a->rays8)
+        REQUIRE(a->depth_map && a->std_map && a->nf_map && a->map_h > 0 && a->map_w > 0,
+                "render_rays_raw: fused build_rays needs depth/std/near_far maps and their size");
+    REQUIRE(a->B > 0 && a->N >= 0 && a->Hr > 1 && a->Wr > 1, "render_rays_raw: bad shape");
+    if (a->vol) REQUIRE(a->D > 0 && a->h > 0 && a->w > 0, "render_rays_raw: bad volume shape");
+    if (a->ray_index) REQUIRE(a->ray_count && a->B == 1, "render_rays_raw: ray_index needs ray_count and B == 1");
+    enerf_render_args_t r = {};
+    r.rays12 = a->rays12; r.tex = a->tex; r.vol = a->vol; r.src_exts = a->src_exts; r.src_ixts = a->src_ixts; r.tar_ext = a->tar_ext;
+    r.packed = a->packed; r.rgb = a->raw; r.depth = a->z; r.weights = nullptr;
+    r.B = a->B; r.N = a->N; r.S = a->S; r.n_samples = a->n_samples; r.depth_inv = a->depth_inv; r.Hr = a->Hr; r.Wr = a->Wr; r.F = a->F;
+    r.D = a->vol ? a->D : 1; r.h = a->vol ? a->h : 1; r.w = a->vol ? a->w : 1;      // (the placement arithmetic still runs; nothing is read)
+    r.render_scale = a->render_scale;
+    r.rays8 = a->rays8; r.depth_map = a->depth_map; r.std_map = a->std_map; r.nf_map = a->nf_map; r.map_h = a->map_h; r.map_w = a->map_w;
+    r.ray_index = a->ray_index; r.ray_count = a->ray_count; r.max_blocks = a->max_blocks;
+    const int rc = launch_render_rays_raw(r, (hipStream_t)stream);
+    if (rc != 0)
+        return fail(ENERF_EINVAL, "render_rays_raw: unsupported configuration (code %d: F=%d S=%d n_samples=%d B=%d)", rc, a->F, a->S,
+                    a->n_samples, a->B);
+    return check_launch("render_rays_raw");
+}
+int enerf_composite_layers(const enerf_composite_layers_t* a, enerf_stream_t stream) {
+    REQUIRE(a, "composite_layers: null args");
+    REQUIRE(a->L >= 1 && a->L <= ENERF_MAX_FG_LAYERS && a->Ns >= 1 && a->L * a->Ns <= 16,
+            "composite_layers: L=%d foreground layers x %d samples unsupported (L in 1..%d, L*n_samples <= 16)", a->L, a->Ns,
+            ENERF_MAX_FG_LAYERS);
+    REQUIRE(a->H > 0 && a->W > 0 && (long long)a->H * a->W * (a->L + 1) * a->Ns * 4 < (1LL << 31), "composite_layers: bad image size");
+    REQUIRE(a->bg_raw && a->bg_z && a->rgb && a->depth && a->weights && a->net_output && a->z_vals, "composite_layers: null pointer");
+    REQUIRE(((uintptr_t)a->bg_raw | (uintptr_t)a->net_output) % 16 == 0, "composite_layers: bg_raw / net_output must be 16-byte aligned");
+    for (int l = 0; l < a->L; ++l) {
+        REQUIRE(a->fg_raw[l] && a->fg_z[l], "composite_layers: layer %d: null pointer", l);
+        REQUIRE((uintptr_t)a->fg_raw[l] % 16 == 0, "composite_layers: layer %d: fg_raw must be 16-byte aligned", l);
+        if (int rc = check_window("composite_layers", a->H, a->W, a->win[l][0], a->win[l][1], a->win[l][2], a->win[l][3])) return rc;
+    }
+    launch_composite_layers(*a, (hipStream_t)stream);
+    return check_launch("composite_layers");
 }
 
 }  // extern "C"

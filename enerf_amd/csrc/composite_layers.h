@@ -1,0 +1,140 @@
+// composite_layers.h — the device code only the composite network (network_composite.py) needs; included by geometry.hip,
+// which holds the softmax moments the windowed regression shares with k_depth_regression.
+//   * k_depth_regression_window  depth_regression (utils.py:658-667) of a prob that exists only inside a layer's box
+//                                (network_composite.py:100-102: F.pad then depth_regression), without the padded prob
+//   * k_window_ray_index         the ray positions of a box in the render image (build_rays_composite), as the index list the
+//                                render kernel's device-side selection reads
+//   * k_composite_layers         parse_layer + raw2outputs_composite (utils.py:875-942): scatter, per-ray depth sort of the
+//                                foreground samples, background appended, alpha compositing — one thread per pixel
+// (The windowed cost volume is k_feature_volume_mp<CQ, true> in volume.hip, the raw-sample render k_render_rays<..., RAW> in
+// render.hip: each is a template value of the kernel it shares its arithmetic with.)
+#pragma once
+#include <math.h>
+
+namespace enerf {
+
+// prob (B, D, wh, ww) of the window at (x0, y0); dv (B, D, h, w); depth / std (B, h, w).  k_depth_regression's mapping (a wave =
+// 16 pixels x 4 depth slices) over the FULL grid; a pixel outside the window runs the same moments with zero logits.
+__global__ __launch_bounds__(256) void k_depth_regression_window(const float* __restrict__ prob, const float* __restrict__ dv, int B,
+                                                                 int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv,
+                                                                 float* __restrict__ depth, float* __restrict__ std) {
+    const int lane = threadIdx.x & 63, sl = lane >> 4;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int hw = h * w, hwp = wh * ww;
+    const long long i = wave * 16 + (lane & 15);
+    const bool ok = i < (long long)B * hw;
+    const long long ii = ok ? i : 0;
+    const int b = (int)(ii / hw), p = (int)(ii - (long long)b * hw);
+    const int y = p / w, x = p - y * w;
+    const bool inside = x >= x0 && x < x0 + ww && y >= y0 && y < y0 + wh;
+    const float* pr = prob + (long long)b * D * hwp + (inside ? (y - y0) * ww + (x - x0) : 0);
+    const float* dp = dv + (long long)b * D * hw + p;
+    float mu, var;
+    if (D <= 16) depth_moments_regs<4>(pr, dp, D, hwp, hw, sl, depth_inv, !inside, mu, var);
+    else depth_moments_regs<16>(pr, dp, D, hwp, hw, sl, depth_inv, !inside, mu, var);          // D <= 64 (the C-ABI layer checks)
+    if (ok && sl == 0) {
+        depth[i] = mu;
+        std[i] = sqrtf(clamp_min(var, 1e-10f));
+    }
+}
+void launch_depth_regression_window(const float* prob, const float* dv, int B, int D, int h, int w, int x0, int y0, int ww, int wh,
+                                    int depth_inv, float* depth, float* std, hipStream_t st) {
+    const long long waves = cdivl((long long)B * h * w, 16);
+    ENERF_LAUNCH(k_depth_regression_window, (unsigned)cdivl(waves, 4), 256, 0, st, prob, dv, B, D, h, w, x0, y0, ww, wh, depth_inv, depth,
+                 std);
+}
+
+// index[r] = the position in the (Hr, Wr) raster of the r-th pixel of the window, raster order; count[0] = ww * wh
+__global__ __launch_bounds__(256) void k_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* __restrict__ index,
+                                                          int* __restrict__ count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) count[0] = ww * wh;
+    if (i >= ww * wh) return;
+    const int yy = i / ww, xx = i - yy * ww;
+    index[i] = (y0 + yy) * Wr + x0 + xx;
+}
+void launch_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* index, int* count, hipStream_t st) {
+    ENERF_LAUNCH_SIMPLE(k_window_ray_index, (unsigned)cdiv(ww * wh, 256), 256, 0, st, x0, y0, ww, wh, Wr, index, count);
+}
+
+using CompositeLayers = enerf_composite_layers_t;
+// Layer l's compact buffers hold the window's pixels in raster order; a pixel outside has zero samples (parse_layer).  With more
+// than one layer the L * Ns foreground samples of the pixel are sorted by depth: an odd-even transposition network over NFP >=
+// L * Ns register slots (padded with +inf, which stay last).  It exchanges NEIGHBOURS and only when the left one is strictly
+// greater, so samples of equal depth keep their concatenation order (layer, then sample): the order is deterministic, where
+// torch.sort promises none.  The background's Ns samples follow unsorted (utils.py:917-918).
+template <int NFP>
+__global__ __launch_bounds__(256) void k_composite_layers(CompositeLayers a) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.H * a.W) return;
+    const int y = p / a.W, x = p - y * a.W;
+    const int Ns = a.Ns, nf = a.L * Ns, T = nf + Ns;
+    int base[ENERF_MAX_FG_LAYERS];                      // the pixel's row in layer l's buffers, or -1
+#pragma unroll
+    for (int l = 0; l < ENERF_MAX_FG_LAYERS; ++l) {
+        const int wx = a.win[l][0], wy = a.win[l][1], ww = a.win[l][2], wh = a.win[l][3];
+        base[l] = (l < a.L && x >= wx && x < wx + ww && y >= wy && y < wy + wh) ? (y - wy) * ww + (x - wx) : -1;
+    }
+    auto row_of = [&](int l) { return l == 0 ? base[0] : (l == 1 ? base[1] : (l == 2 ? base[2] : base[3])); };
+    auto z_of = [&](int l) { return l == 0 ? a.fg_z[0] : (l == 1 ? a.fg_z[1] : (l == 2 ? a.fg_z[2] : a.fg_z[3])); };
+    auto raw_of = [&](int l) { return l == 0 ? a.fg_raw[0] : (l == 1 ? a.fg_raw[1] : (l == 2 ? a.fg_raw[2] : a.fg_raw[3])); };
+    float zk[NFP];
+    int id[NFP];                                        // l * Ns + k of the sample in the slot
+#pragma unroll
+    for (int i = 0; i < NFP; ++i) {
+        zk[i] = INFINITY;
+        id[i] = i;
+        if (i < nf) {
+            const int l = i / Ns, k = i - l * Ns, row = row_of(l);
+            zk[i] = row >= 0 ? z_of(l)[(long long)row * Ns + k] : 0.f;
+            a.z_vals[(long long)p * nf + i] = zk[i];    // z_vals_ori: concatenation order
+        }
+    }
+    if (a.L > 1) {                                      // uniform
+#pragma unroll
+        for (int r = 0; r < NFP; ++r)
+#pragma unroll
+            for (int i = r & 1; i + 1 < NFP; i += 2) {
+                const bool sw = zk[i] > zk[i + 1];
+                const float zl = zk[i], zr = zk[i + 1];
+                const int il = id[i], ir = id[i + 1];
+                zk[i] = sw ? zr : zl; zk[i + 1] = sw ? zl : zr;
+                id[i] = sw ? ir : il; id[i + 1] = sw ? il : ir;
+            }
+    }
+    // alpha compositing (utils.py:922-933): no softmax of the weights
+    float Tacc = 1.f, rgb0 = 0.f, rgb1 = 0.f, rgb2 = 0.f, dep = 0.f, acc = 0.f;
+    auto step = [&](int t, const float4 c, float z) {
+        *reinterpret_cast<float4*>(a.net_output + ((long long)p * T + t) * 4) = c;
+        const float alpha = 1.f - expf(-c.w);
+        const float wgt = alpha * Tacc;
+        Tacc *= (1.f - alpha + 1e-10f);
+        rgb0 += wgt * c.x; rgb1 += wgt * c.y; rgb2 += wgt * c.z;
+        dep += wgt * z;
+        acc += wgt;
+        a.weights[(long long)p * T + t] = wgt;
+    };
+#pragma unroll
+    for (int i = 0; i < NFP; ++i)
+        if (i < nf) {
+            const int l = id[i] / Ns, k = id[i] - l * Ns, row = row_of(l);
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row >= 0) c = *reinterpret_cast<const float4*>(raw_of(l) + ((long long)row * Ns + k) * 4);
+            step(i, c, zk[i]);
+        }
+    for (int k = 0; k < Ns; ++k)
+        step(nf + k, *reinterpret_cast<const float4*>(a.bg_raw + ((long long)p * Ns + k) * 4), a.bg_z[(long long)p * Ns + k]);
+    if (a.white_bkgd) { rgb0 += 1.f - acc; rgb1 += 1.f - acc; rgb2 += 1.f - acc; }
+    a.rgb[(long long)p * 3 + 0] = rgb0; a.rgb[(long long)p * 3 + 1] = rgb1; a.rgb[(long long)p * 3 + 2] = rgb2;
+    a.depth[p] = dep;
+}
+void launch_composite_layers(const CompositeLayers& a, hipStream_t st) {
+    const int nf = a.L * a.Ns;
+    const unsigned grid = (unsigned)cdiv(a.H * a.W, 256);
+    if (nf <= 2) ENERF_LAUNCH_SIMPLE(k_composite_layers<2>, grid, 256, 0, st, a);
+    else if (nf <= 4) ENERF_LAUNCH_SIMPLE(k_composite_layers<4>, grid, 256, 0, st, a);
+    else if (nf <= 8) ENERF_LAUNCH_SIMPLE(k_composite_layers<8>, grid, 256, 0, st, a);
+    else ENERF_LAUNCH_SIMPLE(k_composite_layers<16>, grid, 256, 0, st, a);      // L * Ns <= 16 (the C-ABI layer checks)
+}
+
+}  // namespace enerf

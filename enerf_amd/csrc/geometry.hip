@@ -243,17 +243,19 @@ __device__ __forceinline__ float slice_max(float v) { return group_max4(v); }
 // Softmax moments of one pixel's D planes, register-resident: every plane value is loaded once (all loads in
 // flight together) and exp'd once; lane slice sl handles planes sl, sl+4, ...  The sums run in the same order as
 // the streaming form in k_depth_regression, so the results are bit-identical to it.
+// hwp / hw: the plane strides of prob and of the depth planes (the windowed regression reads a cropped prob: composite_layers.h);
+// zero_logits: this lane's pixel has no prob — its D logits are 0, as in a zero-padded prob (uniform softmax).
 template <int MK>
-__device__ __forceinline__ void depth_moments_regs(const float* pr, const float* dp, int D, int hw, int sl, int depth_inv,
-                                                   float& mu, float& var) {
+__device__ __forceinline__ void depth_moments_regs(const float* pr, const float* dp, int D, int hwp, int hw, int sl, int depth_inv,
+                                                   bool zero_logits, float& mu, float& var) {
     float e[MK], v[MK];
     float m = -INFINITY;
 #pragma unroll
     for (int kk = 0; kk < MK; ++kk) {
         const int k = sl + 4 * kk;
         const bool in = k < D;
-        const long long o = (long long)(in ? k : 0) * hw;
-        const float x = pr[o], d = dp[o];
+        const long long o = (long long)(in ? k : 0) * hw, op = (long long)(in ? k : 0) * hwp;
+        const float x = zero_logits ? 0.f : pr[op], d = dp[o];
         e[kk] = in ? x : -INFINITY;
         v[kk] = depth_inv ? 1.f / clamp_min(d, 1e-6f) : d;
         m = fmaxf(m, e[kk]);
@@ -289,8 +291,8 @@ __global__ __launch_bounds__(256) void k_depth_regression(const float* __restric
     const float* pr = prob + (long long)b * D * hw + p;
     const float* dp = dv + (long long)b * D * hw + p;
     float mu, var;
-    if (D <= 16) depth_moments_regs<4>(pr, dp, D, hw, sl, depth_inv, mu, var);
-    else if (D <= 64) depth_moments_regs<16>(pr, dp, D, hw, sl, depth_inv, mu, var);
+    if (D <= 16) depth_moments_regs<4>(pr, dp, D, hw, hw, sl, depth_inv, false, mu, var);
+    else if (D <= 64) depth_moments_regs<16>(pr, dp, D, hw, hw, sl, depth_inv, false, mu, var);
     else {
         float m = -INFINITY;
         for (int k = sl; k < D; k += 4) m = fmaxf(m, pr[(long long)k * hw]);
@@ -370,8 +372,8 @@ __global__ __launch_bounds__(256) void k_regress_and_values(const float* __restr
         const float* pr = prob_p + (long long)b * Dp * hwp + pcoarse;
         const float* dp = dv_p + (long long)b * Dp * hwp + pcoarse;
         float mu, var;
-        if (Dp <= 16) depth_moments_regs<4>(pr, dp, Dp, hwp, sl, depth_inv_p, mu, var);
-        else depth_moments_regs<16>(pr, dp, Dp, hwp, sl, depth_inv_p, mu, var);          // Dp <= 64 (launcher)
+        if (Dp <= 16) depth_moments_regs<4>(pr, dp, Dp, hwp, hwp, sl, depth_inv_p, false, mu, var);
+        else depth_moments_regs<16>(pr, dp, Dp, hwp, hwp, sl, depth_inv_p, false, mu, var);          // Dp <= 64 (launcher)
         if (okc && sl == 0) {
             const float sd = sqrtf(clamp_min(var, 1e-10f));
             cd[cc] = mu; cs[cc] = sd;
@@ -456,3 +458,5 @@ void launch_build_rays(const float* rays8, const float* depth, const float* std,
 }
 
 }  // namespace enerf
+
+#include "composite_layers.h"      // the composite network's kernels (they share depth_moments_regs)

@@ -278,5 +278,15 @@ long long nerf_packed_floats(int feat_ch_plus3);
 void launch_nerf_pack(const NerfRaw& raw, int F, int viewdir_agg, float* packed, hipStream_t st);
 using RenderArgs = enerf_render_args_t;
 int launch_render_rays(const RenderArgs& a, hipStream_t st);  // returns 0, or <0 for unsupported shapes
+// the RAW instantiations: a.rgb = (n, Ns, 4) samples [r, g, b, sigma], a.depth = (n, Ns) metric sample depths, a.vol may be NULL
+int launch_render_rays_raw(const RenderArgs& a, hipStream_t st);
+
+// ---- the composite network (network_composite.py): volume.hip, composite_layers.h (included by geometry.hip) ----
+void launch_feature_volume_window(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs, int Ws, int D,
+                                  int h, int w, int x0, int y0, int ww, int wh, float* vol, hipStream_t st);
+void launch_depth_regression_window(const float* prob, const float* dv, int B, int D, int h, int w, int x0, int y0, int ww, int wh,
+                                    int depth_inv, float* depth, float* std, hipStream_t st);
+void launch_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* index, int* count, hipStream_t st);
+void launch_composite_layers(const enerf_composite_layers_t& a, hipStream_t st);
 
 }  // namespace enerf

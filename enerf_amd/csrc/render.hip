@@ -176,13 +176,19 @@ template <int R> struct Stage { static constexpr int kTex = 4 * R, kStride = 4 *
 // WPE = waves per SIMD the register budget is sized for (512 / WPE VGPRs): blocks per CU x WAVES / 4
 // BX = 3 / 6 (R = 3 only): the dense layers of the MLP on the bf16 matrix cores with operands split into 2 / 3 bf16 pieces
 // (nerf_layout.h "bf16x3" / "bf16x6"); view_fc (k = 4) and the width-1 heads stay as they are.  BX = 0: fp32 MFMAs.
-template <int R, int S, int WAVES, int WPE, bool PFK = false, bool LEANK = false, int BX = 0>
+// RAW (network_composite.py:29-51, the composite network's render_rays): the kernel ends at the MLP.  Per sample it stores
+// [r, g, b, sigma] to a.rgb, read as (n, Ns, 4), and the sample's metric depth (1 / z at depth_inv levels) to a.depth, read as
+// (n, Ns); a.weights is not touched and nothing is composited (that is k_composite_layers, over all layers' samples).  a.vol may be
+// NULL: that model's MLP ignores the voxel feature, so the eight inputs are zero and no trilinear fetch is issued.  Everything
+// RAW adds sits under `if constexpr`: the other instantiations are the code they were.
+template <int R, int S, int WAVES, int WPE, bool PFK = false, bool LEANK = false, int BX = 0, bool RAW = false>
 __global__ __launch_bounds__(64 * WAVES)
 #ifndef ENERF_EMU
 __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #endif
 void k_render_rays(RenderArgs a) {
     static_assert(BX == 0 || R == 3, "the bf16 image exists for F = 11 only");
+    static_assert(!RAW || (BX == 0 && !PFK), "raw samples come from the exact fp32 kernel, one sample at a time");
     constexpr bool BX3 = BX != 0;                        // (name kept: "the MLP runs on bf16 pieces")
     constexpr int NP = BX == 6 ? 3 : 2;                  // bf16 pieces per operand
     constexpr int TR = (R + 3) / 4;
@@ -417,9 +423,14 @@ void k_render_rays(RenderArgs a) {
                 zo[c] = mul24(min(max(zc, 0), a.D - 1), a.h * a.w);
             }
             __builtin_amdgcn_sched_barrier(0);
+            if (RAW && a.vol == nullptr) {              // uniform; no voxel fetch
 #pragma unroll
-            for (int c = 0; c < 8; ++c)                 // order tnw,tne,tsw,tse,bnw,bne,bsw,bse
-                G.vt[c] = *reinterpret_cast<const float2*>(volb + ((unsigned)(zo[c >> 2] + oxy[c & 3]) * 8u + voff) * 4u);
+                for (int c = 0; c < 8; ++c) G.vt[c] = make_float2(0.f, 0.f);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 8; ++c)             // order tnw,tne,tsw,tse,bnw,bne,bsw,bse
+                    G.vt[c] = *reinterpret_cast<const float2*>(volb + ((unsigned)(zo[c >> 2] + oxy[c & 3]) * 8u + voff) * 4u);
+            }
             // texel channels are gathered QB float4 chunks per tap at a time; R = 9 takes three rounds, two of them in flight
 #pragma unroll
             for (int rd = 0; rd < NBUF; ++rd)
@@ -726,6 +737,29 @@ void k_render_rays(RenderArgs a) {
                 for (int s = 0; s < S; ++s) cl[s] *= se;
             }
 
+            if constexpr (RAW) {
+                // ---------- the sample itself (network_composite.py:46-51): [colour, sigma] and its metric depth ----------
+                const float tk = (Ns == 1) ? 0.5f : linspace01(k, Ns);
+                const float zs = rn + (rf - rn) * tk;
+                if (rok) {
+                    const long long so = ray * Ns + k;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const int c = g * R + r - (a.F - 3);
+                        if (c >= 0 && c < 3) {
+                            float col = x[0][r] * cl[0];
+#pragma unroll
+                            for (int s = 1; s < S; ++s) col += x[s][r] * cl[s];
+                            a.rgb[so * 4 + c] = col;
+                        }
+                    }
+                    if (g == 0) {
+                        a.rgb[so * 4 + 3] = sig;
+                        a.depth[so] = a.depth_inv ? 1.f / zs : zs;
+                    }
+                }
+                continue;
+            }
             // ---------- compositing step (utils.py:584-592) ----------
             float alpha = 1.f - fast_exp(-sig);
             float wgt = alpha * Tacc;
@@ -741,6 +775,7 @@ void k_render_rays(RenderArgs a) {
             for (int kk = 0; kk < NSM; ++kk)
                 if (kk == k) wk[kk] = wgt;
         }
+        if constexpr (RAW) continue;
 
         // ---------- depth from softmaxed weights (utils.py:593-595) + stores ----------
         float m = wk[0];
@@ -786,6 +821,16 @@ static int dispatch_s(const RenderArgs& a, unsigned grid, size_t shmem, hipStrea
         case 2: ENERF_LAUNCH((k_render_rays<R, 2, WAVES, WPE, PFK, LEANK, BX3>), grid, 64 * WAVES, shmem, st, a); return 0;
         case 3: ENERF_LAUNCH((k_render_rays<R, 3, WAVES, WPE, PFK, LEANK, BX3>), grid, 64 * WAVES, shmem, st, a); return 0;
         case 4: ENERF_LAUNCH((k_render_rays<R, 4, WAVES, WPE, PFK, LEANK, BX3>), grid, 64 * WAVES, shmem, st, a); return 0;
+        default: return -3;
+    }
+}
+template <int R, int WAVES, int OCC, bool LEANK>
+static int dispatch_s_raw(const RenderArgs& a, unsigned grid, size_t shmem, hipStream_t st) {
+    constexpr int WPE = (WAVES * OCC + 3) / 4;
+    switch (a.S) {
+        case 2: ENERF_LAUNCH((k_render_rays<R, 2, WAVES, WPE, false, LEANK, 0, true>), grid, 64 * WAVES, shmem, st, a); return 0;
+        case 3: ENERF_LAUNCH((k_render_rays<R, 3, WAVES, WPE, false, LEANK, 0, true>), grid, 64 * WAVES, shmem, st, a); return 0;
+        case 4: ENERF_LAUNCH((k_render_rays<R, 4, WAVES, WPE, false, LEANK, 0, true>), grid, 64 * WAVES, shmem, st, a); return 0;
         default: return -3;
     }
 }
@@ -863,6 +908,41 @@ int launch_render_rays(const RenderArgs& a, hipStream_t st) {
         }
         if (grid == 0) return 0;
         return dispatch_s<9, 8, 1, false, ENERF_R9_LEAN != 0>(a, grid, shmem, st);
+    }
+    return -4;
+}
+
+// The RAW instantiations (see k_render_rays): a.rgb is the (n, Ns, 4) sample buffer, a.depth the (n, Ns) depths, a.vol may be
+// NULL.  One launch shape per F, the exact fp32 ones of the table above that hold any n_samples: 4-wave blocks x 2 per CU at
+// F = 11, one 8-wave block per CU at F = 35.
+int launch_render_rays_raw(const RenderArgs& a, hipStream_t st) {
+    if (a.n_samples < 1 || a.n_samples > 8) return -1;
+    const int R = (a.F + 3) / 4;
+    if ((long long)a.B * a.S * a.Hr * a.Wr * 4 * R >= (1LL << 30) || (long long)a.B * a.D * a.h * a.w * 8 >= (1LL << 30) ||
+        (long long)a.Hr * a.Wr >= (1LL << 23) || (long long)a.h * a.w >= (1LL << 23) || a.D >= (1 << 23))
+        return -5;
+    if (nerf_layout(a.F).total > (R == 3 ? 10560 : 14528)) return -6;
+    const long long ntiles = cdivl((long long)a.B * a.N, 16);
+    const int cus = device_cu_count();
+    auto grid_for = [&](int waves, int occ) {
+        const long long blocks = cdivl(ntiles, waves);
+        long long resident = (long long)cus * occ;
+        if (a.max_blocks > 0 && a.max_blocks < resident) resident = a.max_blocks;
+        return (unsigned)(blocks < resident ? blocks : resident);
+    };
+    if (R == 3) {
+        const size_t shmem = render_shmem<3, ENERF_RENDER_WAVES>(a);
+        if (shmem > 160 * 1024 / ENERF_RENDER_OCC) return -2;
+        const unsigned grid = grid_for(ENERF_RENDER_WAVES, ENERF_RENDER_OCC);
+        if (grid == 0) return 0;
+        return dispatch_s_raw<3, ENERF_RENDER_WAVES, ENERF_RENDER_OCC, false>(a, grid, shmem, st);
+    }
+    if (R == 9) {
+        const size_t shmem = render_shmem<9, 8>(a);
+        if (shmem > 160 * 1024) return -2;
+        const unsigned grid = grid_for(8, 1);
+        if (grid == 0) return 0;
+        return dispatch_s_raw<9, 8, 1, ENERF_R9_LEAN != 0>(a, grid, shmem, st);
     }
     return -4;
 }

@@ -136,11 +136,14 @@ __global__ __launch_bounds__(256) void k_feature_volume(const float* __restrict_
 // one-plane form above lives for two dependent memory round trips and there are ~40 of them per SIMD: neither its VALU count
 // (round 4: -30 % VALU, < 3 % time) nor its lane broadcasts (DPP instead of ds_bpermute: nothing) is what it waits for.
 // Same arithmetic per voxel, bit-identical output.
-template <int CQ>
+// WIN (the composite network's boxed layers, homo_warp_composite utils.py:153-190): (h, w) is a WINDOW of the (hf, wf) grid with its
+// corner at (x0, y0).  The block -> voxel decomposition and the output (B, D, h, w, C) are the window's; the depth planes dv are
+// read at, and the pixel projected from, the voxel's place in the FULL grid — every voxel gets the bits the full launch gives it.
+template <int CQ, bool WIN = false>
 __global__ __launch_bounds__(256) void k_feature_volume_mp(const float* __restrict__ feat, const float* __restrict__ proj,
                                                            const float* __restrict__ dv, int B, int S, int Hs, int Ws,
                                                            int D, int h, int w, float inv_w, float inv_d, int planar,
-                                                           float* __restrict__ vol) {
+                                                           float* __restrict__ vol, int x0, int y0, int hf, int wf) {
     constexpr int C = CQ * 4, NPL = 2;
     const int xcd = blockIdx.x;                                    // gridDim.x == 8: one row band per XCD (see above)
     const int rb = (h + 7) >> 3;
@@ -164,9 +167,10 @@ __global__ __launch_bounds__(256) void k_feature_volume_mp(const float* __restri
 #pragma unroll
     for (int q = 0; q < NPL; ++q) {
         vox[q] = (unsigned)mul24((int)((pl0 + q) * (unsigned)h) + y, w) + (unsigned)x;
-        depth[q] = dv[vox[q]];
+        if constexpr (WIN) depth[q] = dv[(unsigned)mul24((int)((pl0 + q) * (unsigned)hf) + y0 + y, wf) + (unsigned)(x0 + x)];
+        else depth[q] = dv[vox[q]];
     }
-    const float fx = (float)x, fy = (float)y;
+    const float fx = (float)(WIN ? x0 + x : x), fy = (float)(WIN ? y0 + y : y);
     const float inv_half_w = 1.f / (float)((Ws - 1) / 2.0), inv_half_h = 1.f / (float)((Hs - 1) / 2.0);
     const unsigned img = (unsigned)(Hs * Ws * C);
     float4 s1[NPL], s2[NPL];
@@ -245,9 +249,9 @@ void launch_feature_volume(const float* feat_nhwc, const float* proj, const floa
     if (ENERF_VOL_NPL == 2 && D % 2 == 0) {                       // two planes per wave
         const dim3 grid2(8, (unsigned)cdiv(rb * w, vpb), (unsigned)(B * D / 2));
         switch (C) {
-            case 32: ENERF_LAUNCH(k_feature_volume_mp<8>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); return;
-            case 16: ENERF_LAUNCH(k_feature_volume_mp<4>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); return;
-            case 8: ENERF_LAUNCH(k_feature_volume_mp<2>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); return;
+            case 32: ENERF_LAUNCH(k_feature_volume_mp<8>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
+            case 16: ENERF_LAUNCH(k_feature_volume_mp<4>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
+            case 8: ENERF_LAUNCH(k_feature_volume_mp<2>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
             default: return;   // validated by the C-ABI layer
         }
     }
@@ -256,6 +260,20 @@ void launch_feature_volume(const float* feat_nhwc, const float* proj, const floa
         case 32: ENERF_LAUNCH(k_feature_volume<8>, grid, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); break;
         case 16: ENERF_LAUNCH(k_feature_volume<4>, grid, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); break;
         case 8: ENERF_LAUNCH(k_feature_volume<2>, grid, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol); break;
+        default: break;   // validated by the C-ABI layer
+    }
+}
+
+// The window (x0, y0, ww, wh) of the (h, w) grid: vol (B, D, wh, ww, C), channels-last.  D is even (the C-ABI layer checks D % 4 == 0).
+void launch_feature_volume_window(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs, int Ws, int D,
+                                  int h, int w, int x0, int y0, int ww, int wh, float* vol, hipStream_t st) {
+    const int rb = (wh + 7) / 8;
+    const int vpb = 256 / (C / 4);
+    const float inv_w = 1.f / (float)ww, inv_d = 1.f / (float)D;
+    const dim3 grid2(8, (unsigned)cdiv(rb * ww, vpb), (unsigned)(B * D / 2));
+    switch (C) {
+        case 32: ENERF_LAUNCH((k_feature_volume_mp<8, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w); break;
+        case 16: ENERF_LAUNCH((k_feature_volume_mp<4, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w); break;
         default: break;   // validated by the C-ABI layer
     }
 }

@@ -93,6 +93,24 @@ class RenderArgs(C.Structure):
                    ("scatter_rgb", _i), ("max_blocks", _i)])
 
 
+class RenderRawArgs(C.Structure):
+    """``enerf_render_raw_args_t``."""
+    _fields_ = ([(n, _f) for n in ("rays12", "rays8", "depth_map", "std_map", "nf_map")] + [("map_h", _i), ("map_w", _i)]
+                + [(n, _f) for n in ("tex", "vol", "src_exts", "src_ixts", "tar_ext", "packed", "raw", "z")]
+                + [(n, _i) for n in ("B", "N", "S", "n_samples", "depth_inv", "Hr", "Wr", "F", "D", "h", "w")]
+                + [("render_scale", _fl), ("ray_index", C.c_void_p), ("ray_count", C.c_void_p), ("max_blocks", _i)])
+
+
+MAX_FG_LAYERS = 4
+
+
+class CompositeLayersArgs(C.Structure):
+    """``enerf_composite_layers_t``."""
+    _fields_ = ([("fg_raw", C.c_void_p * MAX_FG_LAYERS), ("fg_z", C.c_void_p * MAX_FG_LAYERS), ("win", (_i * 4) * MAX_FG_LAYERS),
+                 ("bg_raw", _f), ("bg_z", _f)] + [(n, _i) for n in ("L", "Ns", "H", "W", "white_bkgd")]
+                + [(n, _f) for n in ("rgb", "depth", "weights", "net_output", "z_vals")])
+
+
 MAX_LEVELS = 3
 STAGE_COUNT = 2 + 6 * MAX_LEVELS
 STAGE_NAMES = ["begin", "feature_net"] + [f"{n}_{i}" for i in range(MAX_LEVELS)
@@ -289,12 +307,26 @@ _SIGNATURES = {
     "enerf_forward_cached": (_i, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct), C.c_void_p, _f]),
     "enerf_ingest_views_u8": (_i, [C.c_void_p, C.c_void_p, _i, _i, _i, _i, _f, _f]),
     "enerf_bounds_near_far": (_i, [_f, _i, _f, _i, _fl, _f, _f]),
+    "enerf_build_feature_volume_window": (_i, [_f, _f, _f] + [_i] * 12 + [_f, _f]),
+    "enerf_depth_regression_window": (_i, [_f, _f] + [_i] * 9 + [_f, _f, _f]),
+    "enerf_window_ray_index": (_i, [_i] * 6 + [C.c_void_p, C.c_void_p, _f]),
+    "enerf_render_rays_raw": (_i, [C.POINTER(RenderRawArgs), _f]),
+    "enerf_composite_layers": (_i, [C.POINTER(CompositeLayersArgs), _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 class EnerfError(RuntimeError):
     pass
+
+
+def _out(out, shape, device, what):
+    """``out`` if given — checked to be a contiguous float32 tensor of ``shape`` on ``device`` — else a fresh tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise EnerfError(f"{what}: out must be a contiguous float32 tensor of shape {tuple(shape)} on {device}")
+    return out
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -431,29 +463,29 @@ class EnerfLib:
                                                self.stream_of(src_inps)), "feature_net")
         return f0, f1, f2, workspace
 
-    def pack_texels_cl(self, feat_cl, src_inps, Hr, Wr):
+    def pack_texels_cl(self, feat_cl, src_inps, Hr, Wr, out=None):
         n_img, hf, wf, Cf = feat_cl.shape
         if (hf, wf) != (Hr, Wr):
             raise EnerfError("pack_texels_cl: features must already be at the render resolution")
         H, W = src_inps.shape[-2:]
         tex = 4 * ((Cf + 3 + 3) // 4)
-        out = torch.empty((n_img, Hr, Wr, tex), dtype=torch.float32, device=feat_cl.device)
+        out = _out(out, (n_img, Hr, Wr, tex), feat_cl.device, "pack_texels_cl")
         self._check(self.dll.enerf_pack_texels_cl(_ptr(feat_cl), Cf, _ptr(src_inps), H, W, Hr, Wr, tex, n_img, _ptr(out),
                                                   self.stream_of(out)), "pack_texels_cl")
         return out
 
-    def get_proj_mats(self, src_ixts, src_exts, tar_ixt, tar_ext, src_scale, tar_scale):
+    def get_proj_mats(self, src_ixts, src_exts, tar_ixt, tar_ext, src_scale, tar_scale, out=None):
         B, S = src_ixts.shape[:2]
-        proj = torch.empty((B, S, 3, 4), dtype=torch.float32, device=src_ixts.device)
+        proj = _out(out, (B, S, 3, 4), src_ixts.device, "get_proj_mats")
         self._check(self.dll.enerf_get_proj_mats(_ptr(src_ixts), _ptr(src_exts), _ptr(tar_ixt), _ptr(tar_ext), B, S,
                                                  float(src_scale), float(tar_scale), _ptr(proj),
                                                  self.stream_of(proj)), "get_proj_mats")
         return proj
 
-    def get_depth_values(self, near_far, prev, B, D, h, w, depth_inv):
+    def get_depth_values(self, near_far, prev, B, D, h, w, depth_inv, out=None):
         dev = near_far.device
-        dv = torch.empty((B, D, h, w), dtype=torch.float32, device=dev)
-        nf = torch.empty((B, 2, h, w), dtype=torch.float32, device=dev)
+        dv = _out(None if out is None else out[0], (B, D, h, w), dev, "get_depth_values")
+        nf = _out(None if out is None else out[1], (B, 2, h, w), dev, "get_depth_values")
         if prev is None:
             pd = ps = pn = None
             hp = wp = 0
@@ -484,10 +516,10 @@ class EnerfLib:
                                               self.stream_of(dv)), "level_prep")
         return proj, dv, nf
 
-    def build_feature_volume(self, feat_cl, proj, dv, Cc):
+    def build_feature_volume(self, feat_cl, proj, dv, Cc, out=None):
         B, S, Hs, Ws = feat_cl.shape[:4]
         _, D, h, w = dv.shape
-        vol = torch.empty((B, D, h, w, Cc), dtype=torch.float32, device=dv.device)
+        vol = _out(out, (B, D, h, w, Cc), dv.device, "build_feature_volume")
         self._check(self.dll.enerf_build_feature_volume(_ptr(feat_cl), _ptr(proj), _ptr(dv), B, S, Cc, Hs, Ws, D, h, w,
                                                         _ptr(vol), self.stream_of(vol)), "build_feature_volume")
         return vol
@@ -498,22 +530,22 @@ class EnerfLib:
         self._check(self.dll.enerf_cost_reg_pack(C.byref(raw), _ptr(packed), self.stream_of(packed)), "cost_reg_pack")
         return packed
 
-    def cost_reg(self, packed, in_channels, full, vol, workspace=None, options=None):
+    def cost_reg(self, packed, in_channels, full, vol, workspace=None, options=None, out=None):
         B, D, h, w, _ = vol.shape
         need = self.dll.enerf_cost_reg_workspace_bytes(int(full), B, D, h, w)
         if workspace is None or workspace.numel() * 4 < need:
             workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=vol.device)
-        feat = torch.empty((B, D, h, w, 8), dtype=torch.float32, device=vol.device)
-        prob = torch.empty((B, D, h, w), dtype=torch.float32, device=vol.device)
+        feat = _out(None if out is None else out[0], (B, D, h, w, 8), vol.device, "cost_reg")
+        prob = _out(None if out is None else out[1], (B, D, h, w), vol.device, "cost_reg")
         self._check(self.dll.enerf_cost_reg(_ptr(packed), in_channels, int(full), _ptr(vol), B, D, h, w, _ptr(feat),
                                             _ptr(prob), _ptr(workspace), workspace.numel() * 4, _opt(options),
                                             self.stream_of(vol)), "cost_reg")
         return feat, prob
 
-    def depth_regression(self, prob, dv, depth_inv):
+    def depth_regression(self, prob, dv, depth_inv, out=None):
         B, D, h, w = prob.shape
-        depth = torch.empty((B, h, w), dtype=torch.float32, device=prob.device)
-        std = torch.empty_like(depth)
+        depth = _out(None if out is None else out[0], (B, h, w), prob.device, "depth_regression")
+        std = _out(None if out is None else out[1], (B, h, w), prob.device, "depth_regression")
         self._check(self.dll.enerf_depth_regression(_ptr(prob), _ptr(dv), B, D, h, w, int(depth_inv), _ptr(depth),
                                                     _ptr(std), self.stream_of(prob)), "depth_regression")
         return depth, std
@@ -583,6 +615,115 @@ class EnerfLib:
                        None if ray_count is None else ray_count.data_ptr(), int(bool(scatter_rgb)), int(max_blocks))
         self._check(self.dll.enerf_render_rays(C.byref(a), self.stream_of(rays12)), "render_rays")
         return rgb, depth, weights
+
+    # -- the composite network (network_composite.py): windows are (x0, y0, ww, wh) in pixels of the grid they are cut from ------
+    def build_feature_volume_window(self, feat_cl, proj, dv, Cc, window, out=None):
+        """The cost volume of the voxels inside ``window`` of dv's (h, w) grid: (B, D, wh, ww, Cc), the bits of the full volume."""
+        B, S, Hs, Ws = feat_cl.shape[:4]
+        _, D, h, w = dv.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        vol = _out(out, (B, D, max(wh, 0), max(ww, 0), Cc), dv.device, "build_feature_volume_window")
+        self._check(self.dll.enerf_build_feature_volume_window(_ptr(feat_cl), _ptr(proj), _ptr(dv), B, S, Cc, Hs, Ws, D, h, w, x0, y0, ww,
+                                                               wh, _ptr(vol), self.stream_of(vol)), "build_feature_volume_window")
+        return vol
+
+    def depth_regression_window(self, prob, dv, depth_inv, window, out=None):
+        """depth_regression of ``prob`` (B, D, wh, ww) zero-padded to dv's (B, D, h, w) grid, without the padded tensor."""
+        B, D, h, w = dv.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        if tuple(prob.shape) != (B, D, wh, ww):
+            raise EnerfError(f"depth_regression_window: prob {tuple(prob.shape)} is not (B, D, wh, ww) = {(B, D, wh, ww)}")
+        depth = _out(None if out is None else out[0], (B, h, w), dv.device, "depth_regression_window")
+        std = _out(None if out is None else out[1], (B, h, w), dv.device, "depth_regression_window")
+        self._check(self.dll.enerf_depth_regression_window(_ptr(prob), _ptr(dv), B, D, h, w, x0, y0, ww, wh, int(depth_inv), _ptr(depth),
+                                                           _ptr(std), self.stream_of(dv)), "depth_regression_window")
+        return depth, std
+
+    def window_ray_index(self, window, Hr, Wr, device, out=None):
+        """(index, count) on the device for render_rays_raw's selection: the window's pixels in the (Hr, Wr) raster, raster order."""
+        x0, y0, ww, wh = (int(v) for v in window)
+        index, count = out if out is not None else (torch.empty((max(ww * wh, 1),), dtype=torch.int32, device=device),
+                                                    torch.empty((1,), dtype=torch.int32, device=device))
+        if index.dtype != torch.int32 or count.dtype != torch.int32 or index.numel() < ww * wh or count.numel() < 1:
+            raise EnerfError("window_ray_index: out=(index, count) must be int32 with ww*wh entries and one")
+        self._check(self.dll.enerf_window_ray_index(x0, y0, ww, wh, int(Hr), int(Wr), index.data_ptr(), count.data_ptr(),
+                                                    self.stream_of(index)), "window_ray_index")
+        return index, count
+
+    def render_rays_raw(self, rays, tex, vol, src_exts, src_ixts, tar_ext, packed, *, n_samples, depth_inv, F, render_scale, maps=None,
+                        max_blocks=0, ray_index=None, ray_count=None, n_out=None, out=None):
+        """The render kernel up to the MLP: ``raw`` (B, n, n_samples, 4) = [r, g, b, sigma] and ``z`` (B, n, n_samples), the samples'
+        metric depths.  ``rays`` as in :meth:`render_rays`; ``vol`` may be None (the MLP's eight voxel inputs are then zero).
+        With ``ray_index`` / ``ray_count`` (B == 1) rows are compacted; ``n_out`` is then the number of rows to allocate."""
+        B, N = rays.shape[:2]
+        if (rays.shape[-1] != 12) != (maps is not None):
+            raise EnerfError("render_rays_raw: pass (B,N,12) rays, or (B,N,8) rays together with maps=(depth,std,near_far)")
+        if (ray_index is None) != (ray_count is None):
+            raise EnerfError("render_rays_raw: pass both ray_index and ray_count or neither")
+        S, Hr, Wr = tex.shape[1:4]
+        D, h, w = vol.shape[1:4] if vol is not None else (0, 0, 0)
+        dev = rays.device
+        n = N if n_out is None else int(n_out)
+        if out is None:
+            raw = torch.empty((B, n, n_samples, 4), dtype=torch.float32, device=dev)
+            z = torch.empty((B, n, n_samples), dtype=torch.float32, device=dev)
+        else:
+            raw, z = out
+            if tuple(raw.shape) != (B, n, n_samples, 4) or tuple(z.shape) != (B, n, n_samples):
+                raise EnerfError("render_rays_raw: out=(raw, z) must be (B,n,n_samples,4), (B,n,n_samples)")
+        if ray_index is not None:
+            for t in (ray_index, ray_count):
+                if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                    raise EnerfError("render_rays_raw: ray_index / ray_count must be contiguous int32 on the rays' device")
+            if n > ray_index.numel() or n > N:
+                raise EnerfError("render_rays_raw: more output rows than selectable rays")
+        elif n != N:
+            raise EnerfError("render_rays_raw: n_out needs ray_index")
+        a = RenderRawArgs()
+        if maps is None:
+            a.rays12 = _ptr(rays)
+        else:
+            md, ms, mn = maps
+            a.rays8, a.depth_map, a.std_map, a.nf_map = _ptr(rays), _ptr(md), _ptr(ms), _ptr(mn)
+            a.map_h, a.map_w = int(md.shape[-2]), int(md.shape[-1])
+        a.tex, a.vol, a.src_exts, a.src_ixts, a.tar_ext = _ptr(tex), _ptr(vol), _ptr(src_exts), _ptr(src_ixts), _ptr(tar_ext)
+        a.packed, a.raw, a.z = _ptr(packed), _ptr(raw), _ptr(z)
+        a.B, a.N, a.S, a.n_samples, a.depth_inv, a.Hr, a.Wr, a.F = B, N, S, int(n_samples), int(depth_inv), Hr, Wr, int(F)
+        a.D, a.h, a.w, a.render_scale, a.max_blocks = D, h, w, float(render_scale), int(max_blocks)
+        if ray_index is not None:
+            a.ray_index, a.ray_count = ray_index.data_ptr(), ray_count.data_ptr()
+        self._check(self.dll.enerf_render_rays_raw(C.byref(a), self.stream_of(rays)), "render_rays_raw")
+        return raw, z
+
+    def composite_layers(self, fg, windows, bg, H, W, white_bkgd=False, out=None):
+        """parse_layer + raw2outputs_composite: ``fg`` = [(raw (n_l, Ns, 4), z (n_l, Ns)), ...] per foreground layer, the rows being the
+        pixels of ``windows[l]`` = (x0, y0, ww, wh) in raster order; ``bg`` = (raw (H*W, Ns, 4), z (H*W, Ns)).  Returns a dict with
+        rgb (N, 3), depth (N), weights (N, T), net_output (N, T, 4) and z_vals (N, L*Ns), N = H*W, T = (L+1)*Ns.  The reference's
+        ``idx`` (torch.sort's permutation) is not returned: equal depths are ordered by layer, then sample, here, and torch.sort
+        promises no order for them."""
+        L, (bg_raw, bg_z) = len(fg), bg
+        Ns, N, dev = int(bg_z.shape[-1]), H * W, bg_z.device
+        if L > MAX_FG_LAYERS or len(windows) != L:
+            raise EnerfError(f"composite_layers: {L} foreground layers, {len(windows)} windows (at most {MAX_FG_LAYERS}, one window each)")
+        if bg_raw.numel() != N * Ns * 4 or bg_z.numel() != N * Ns:
+            raise EnerfError("composite_layers: the background covers the whole (H, W) image")
+        a = CompositeLayersArgs(L=L, Ns=Ns, H=int(H), W=int(W), white_bkgd=int(bool(white_bkgd)))
+        for l, ((raw, z), win) in enumerate(zip(fg, windows)):
+            x0, y0, ww, wh = (int(v) for v in win)
+            if raw.numel() != max(ww * wh, 0) * Ns * 4 or z.numel() != max(ww * wh, 0) * Ns:
+                raise EnerfError(f"composite_layers: layer {l}: buffers do not hold the window's {ww}x{wh} pixels x {Ns} samples")
+            a.fg_raw[l], a.fg_z[l] = _ptr(raw), _ptr(z)
+            a.win[l][0], a.win[l][1], a.win[l][2], a.win[l][3] = x0, y0, ww, wh
+        T = (L + 1) * Ns
+        shapes = {"rgb": (N, 3), "depth": (N,), "weights": (N, T), "net_output": (N, T, 4), "z_vals": (N, L * Ns)}
+        res = out if out is not None else {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in shapes.items()}
+        for k, sh in shapes.items():
+            if tuple(res[k].shape) != sh:
+                raise EnerfError(f"composite_layers: out[{k!r}] must be {sh}")
+            setattr(a, k, _ptr(res[k]))
+        a.bg_raw, a.bg_z = _ptr(bg_raw), _ptr(bg_z)
+        self._check(self.dll.enerf_composite_layers(C.byref(a), self.stream_of(bg_z)), "composite_layers")
+        return res
 
 
     # -- backward kernels (training path; wrapped by enerf_amd/autograd.py) -----------------------------
@@ -1181,10 +1322,10 @@ class EnerfLib:
         self._check(self.dll.enerf_forward_cached(C.byref(args), C.byref(cache), view_idx_ptr, stream), "forward_cached")
 
     # -- the steps before / after the path ---------------------------------
-    def gen_rays(self, tar_ext, tar_ixt, Hr, Wr, scale):
+    def gen_rays(self, tar_ext, tar_ixt, Hr, Wr, scale, out=None):
         """lib/datasets/enerf_utils.py:61-71 (full image) on device -> (B, Hr*Wr, 8)."""
         B = tar_ext.shape[0]
-        rays = torch.empty((B, Hr * Wr, 8), dtype=torch.float32, device=tar_ext.device)
+        rays = _out(out, (B, Hr * Wr, 8), tar_ext.device, "gen_rays")
         self._check(self.dll.enerf_gen_rays(_ptr(tar_ext), _ptr(tar_ixt), B, Hr, Wr, float(scale), _ptr(rays),
                                             self.stream_of(rays)), "gen_rays")
         return rays

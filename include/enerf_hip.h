@@ -798,6 +798,66 @@ int enerf_ingest_views_u8(const unsigned char* img, const unsigned char* mask, i
 int enerf_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
                           enerf_stream_t stream);
 
+/* ---- the composite network (network_composite.py: boxed foreground layers over a background; ABI v11 grew by these five entries;
+ * new symbols only, the version number is unchanged).  B == 1 wherever a window's rays are selected, as in the reference, which
+ * reads batch['bbox'][0] for every batch element.  A window is (x0, y0, ww, wh) in pixels of the grid it is cut from.
+ *   enerf_build_feature_volume_window   homo_warp_composite + variance (utils.py:153-190): enerf_build_feature_volume of the
+ *       voxels inside the window of the (h, w) grid only.  depth_values (B,D,h,w) is the FULL grid's; vol (B,D,wh,ww,C)
+ *       channels-last, C in {16, 32}.  Every voxel holds exactly the bits enerf_build_feature_volume gives it on the full grid.
+ *       ENERF_EINVAL: null pointer, window outside the grid, wh / ww / D not divisible by 4.
+ *   enerf_depth_regression_window       F.pad(prob) + depth_regression (network_composite.py:100-102): prob (B,D,wh,ww) of the
+ *       window, depth_values (B,D,h,w) -> depth, std (B,h,w).  Outside the window the logits are zero (a uniform softmax), the
+ *       padded prob is never built; bit-identical to enerf_depth_regression on the zero-padded prob.  D <= 64.
+ *   enerf_window_ray_index              the positions of the window's pixels in the (Hr, Wr) ray raster, raster order, as
+ *       enerf_render_rays' device-side selection reads them: index (>= ww*wh) int32, count (1) int32, both on the device.
+ *   enerf_render_rays_raw               Network.render_rays of network_composite.py:29-51: the render kernel up to and including the
+ *       MLP.  raw (n,n_samples,4) = [r, g, b, sigma] and z (n,n_samples) = the samples' metric depth (1 / z at depth_inv levels), rows
+ *       compacted when ray_index is given (row r <- ray ray_index[r], rows >= *ray_count untouched).  vol may be NULL (then D, h, w
+ *       are ignored): the eight voxel inputs of the MLP are zero and no voxel is fetched — that model's NeRF ignores them, and its
+ *       weights are packed with zero columns in their place.  Exact fp32 only.
+ *   enerf_composite_layers              parse_layer + raw2outputs_composite (utils.py:875-942), one thread per pixel of the (H, W)
+ *       render image: layer l's samples inside its window, zeros outside; with L > 1 the L*n_samples foreground samples are sorted
+ *       by depth (stable: samples of equal depth keep layer-then-sample order — torch.sort promises no order there, so the
+ *       reference's `idx` is not an output); the background's samples follow; alpha compositing WITHOUT a softmax of the weights.
+ *       With T = (L+1)*n_samples: rgb (N,3), depth (N), weights (N,T), net_output (N,T,4) in composited order, z_vals
+ *       (N,L*n_samples) in concatenation order, N = H*W.  L in 1..4 and L*n_samples <= 16, else ENERF_EINVAL. */
+#define ENERF_MAX_FG_LAYERS 4
+int enerf_build_feature_volume_window(const float* feat, const float* proj, const float* depth_values, int B, int S, int C, int Hs,
+                                      int Ws, int D, int h, int w, int x0, int y0, int ww, int wh, float* vol, enerf_stream_t stream);
+int enerf_depth_regression_window(const float* prob, const float* depth_values, int B, int D, int h, int w, int x0, int y0, int ww,
+                                  int wh, int depth_inv, float* depth, float* std, enerf_stream_t stream);
+int enerf_window_ray_index(int x0, int y0, int ww, int wh, int Hr, int Wr, int* index, int* count, enerf_stream_t stream);
+typedef struct {
+    const float* rays12;   /* (B,N,12), or NULL with rays8 + maps (the fused build_rays of enerf_render_args_t) */
+    const float* rays8;
+    const float *depth_map, *std_map, *nf_map;
+    int map_h, map_w;
+    const float* tex;      /* (B,S,Hr,Wr,TEX) */
+    const float* vol;      /* (B,D,h,w,8) or NULL */
+    const float* src_exts; /* (B,S,4,4) */
+    const float* src_ixts; /* (B,S,3,3) */
+    const float* tar_ext;  /* (B,4,4) */
+    const float* packed;   /* enerf_nerf_pack output */
+    float* raw;            /* (B,N,n_samples,4) */
+    float* z;              /* (B,N,n_samples) */
+    int B, N, S, n_samples, depth_inv, Hr, Wr, F, D, h, w;
+    float render_scale;
+    const int* ray_index;  /* optional device-side selection, B must be 1 */
+    const int* ray_count;
+    int max_blocks;        /* > 0 caps the number of persistent blocks */
+} enerf_render_raw_args_t;
+int enerf_render_rays_raw(const enerf_render_raw_args_t* args, enerf_stream_t stream);
+typedef struct {
+    const float* fg_raw[ENERF_MAX_FG_LAYERS]; /* layer l: (win[l][2]*win[l][3], n_samples, 4), the window's pixels in raster order */
+    const float* fg_z[ENERF_MAX_FG_LAYERS];   /* (win[l][2]*win[l][3], n_samples) */
+    int win[ENERF_MAX_FG_LAYERS][4];          /* x0, y0, ww, wh in the (H, W) render image */
+    const float* bg_raw;                      /* (H*W, n_samples, 4) */
+    const float* bg_z;                        /* (H*W, n_samples) */
+    int L, Ns, H, W, white_bkgd;              /* Ns = n_samples */
+    float *rgb, *depth, *weights, *net_output, *z_vals;
+} enerf_composite_layers_t;
+int enerf_composite_layers(const enerf_composite_layers_t* args, enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
