@@ -3,8 +3,10 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "kernels.h"
+#include "prep_job.h"
 
 using namespace enerf;
 
@@ -358,12 +360,56 @@ int enerf_render_rays(const enerf_render_args_t* a, enerf_stream_t stream) {
 }
 
 
-// ---- the composite network's entries (include/enerf_hip.h) ----
+}  // extern "C"
+namespace enerf {
+// ---- the composite network: window check and the preparation job, then its entries (include/enerf_hip.h) ----
 static int check_window(const char* what, int h, int w, int x0, int y0, int ww, int wh) {
     REQUIRE(h > 0 && w > 0 && ww > 0 && wh > 0 && x0 >= 0 && y0 >= 0 && (long long)x0 + ww <= w && (long long)y0 + wh <= h,
             "%s: window (x0 %d, y0 %d, %d x %d) outside the %d x %d grid", what, x0, y0, ww, wh, w, h);
     return ENERF_OK;
 }
+// enerf_composite_prep's arguments -> the job k_composite_prep runs: one block-range per set of planes and per window
+int composite_prep_job(const enerf_composite_prep_t* a, CompositePrep* job) {
+    REQUIRE(a && job, "composite_prep: null args");
+    REQUIRE(a->L >= 1 && a->L <= ENERF_MAX_FG_LAYERS, "composite_prep: L=%d foreground layers unsupported (1..%d)", a->L, ENERF_MAX_FG_LAYERS);
+    REQUIRE(a->S >= 1 && a->num_levels >= 1 && a->num_levels <= ENERF_MAX_LEVELS, "composite_prep: S=%d, num_levels=%d unsupported (S >= 1, 1..%d levels)",
+            a->S, a->num_levels, ENERF_MAX_LEVELS);
+    REQUIRE(a->src_ixts && a->src_exts && a->tar_ixt && a->tar_ext && a->near_far, "composite_prep: null camera / near_far pointer");
+    REQUIRE(a->fg_planes > 0 && a->bg_planes > 0 && a->h > 0 && a->w > 0, "composite_prep: planes (%d, %d) / grid %d x %d empty", a->fg_planes,
+            a->bg_planes, a->w, a->h);
+    REQUIRE((long long)(a->fg_planes > a->bg_planes ? a->fg_planes : a->bg_planes) * a->h * a->w < (1LL << 31), "composite_prep: grid too large");
+    CompositePrep& J = *job;
+    memset(&J, 0, sizeof(J));
+    for (int i = 0; i < a->num_levels; ++i) {
+        REQUIRE(a->proj[i], "composite_prep: proj[%d] is null", i);
+        J.pj[i] = ProjJob{a->src_ixts, a->src_exts, a->tar_ixt, a->tar_ext, a->proj[i], a->S, a->src_scale[i], a->tar_scale[i]};
+    }
+    int nb = 0;
+    J.n_cas = a->L + 1; J.h = a->h; J.w = a->w; J.depth_inv = a->depth_inv;
+    for (int c = 0; c <= a->L; ++c) {
+        REQUIRE(a->dv[c] && a->nf[c], "composite_prep: dv[%d] / nf[%d] is null", c, c);
+        const int D = c < a->L ? a->fg_planes : a->bg_planes;
+        const int blocks = composite_prep_job_blocks((long long)D * a->h * a->w, 256);
+        J.cas[c] = CompositePrep::Planes{a->near_far + 2 * c, a->dv[c], a->nf[c], D, nb, blocks};
+        nb += blocks;
+    }
+    for (int i = 0; i < a->num_levels; ++i) {
+        if (a->Hr[i] == 0) continue;
+        REQUIRE((long long)a->Hr[i] * a->Wr[i] < (1LL << 31), "composite_prep: ray raster of level %d too large", i);
+        for (int l = 0; l < a->L; ++l) {
+            const int* wn = a->win[i][l];
+            REQUIRE(a->index[i][l] && a->count[i][l], "composite_prep: index[%d][%d] / count[%d][%d] is null", i, l, i, l);
+            if (int rc = check_window("composite_prep", a->Hr[i], a->Wr[i], wn[0], wn[1], wn[2], wn[3])) return rc;
+            const int blocks = composite_prep_job_blocks((long long)wn[2] * wn[3], 256);
+            J.win[J.n_win++] = CompositePrep::Window{wn[0], wn[1], wn[2], wn[3], a->Wr[i], nb, blocks, a->index[i][l], a->count[i][l]};
+            nb += blocks;
+        }
+    }
+    J.nblocks = nb;
+    return ENERF_OK;
+}
+}  // namespace enerf
+extern "C" {
 int enerf_build_feature_volume_window(const float* feat, const float* proj, const float* depth_values, int B, int S, int C, int Hs,
                                       int Ws, int D, int h, int w, int x0, int y0, int ww, int wh, float* vol, enerf_stream_t stream) {
     REQUIRE(feat && proj && depth_values && vol, "build_feature_volume_window: null pointer");
@@ -438,6 +484,12 @@ int enerf_composite_layers(const enerf_composite_layers_t* a, enerf_stream_t str
     }
     launch_composite_layers(*a, (hipStream_t)stream);
     return check_launch("composite_layers");
+}
+int enerf_composite_prep(const enerf_composite_prep_t* a, enerf_stream_t stream) {
+    CompositePrep job;
+    if (int rc = composite_prep_job(a, &job)) return rc;
+    launch_composite_prep(job, (hipStream_t)stream);
+    return check_launch("composite_prep");
 }
 
 }  // extern "C"

@@ -3,7 +3,9 @@
 // loop the reference runs in Python is a plan (buffer carving) + ~30 kernel enqueues here, in one C call, with no host
 // synchronisation: on the caller's stream, with the leaves of the frame forked onto a side lane (side_lane.h) and joined again.
 // Layout: kernels of this file; FeatDims / make_plan (shapes, workspace); FrameRun (one member function per stage) and
-// run_frame (their sequence); the C entries.
+// run_frame (their sequence); the composite network's frame in the same form (make_composite_plan, CompositeRun, run_composite:
+// enerf_forward_composite); the C entries.
+#include <stdint.h>
 #include <string.h>
 
 #include "kernels.h"
@@ -730,6 +732,382 @@ int run_frame(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, co
     }
     return R.finish();
 }
+
+// =====================================================================================================================
+// The composite network's frame (enerf_forward_composite; network_composite.py:77-146): L boxed foreground cascades over one
+// background cascade, merged per rendered level by enerf_composite_layers.  Same shape as the driver above — a plan that refuses
+// everything the host can see and carves the workspace, one CompositeRun on the stack with one member function per stage,
+// run_composite their sequence — but the stages are the library's separate C entries, called exactly as a host stitching the
+// frame together itself would call them (the windowed volume and regression for a layer, cost_reg on a channels-last volume, the
+// raw render without a voxel volume), so the frame's bits are that host's bits.  Only the camera-only preparation differs: one
+// k_composite_prep launch at the head of the frame instead of a launch per level, cascade and window.
+//
+// Streams (side_lane.h): cascade L (the background) and feature_net_bg stay on the caller's stream; feature_net, the texel packs of
+// src_inps and layer l's cascade + raw renders go to `side` (even l) or `render` (odd l), forked behind the preparation and
+// joined in front of every rendered level's merge and at every exit.
+//
+// Workspace regions by chain — chains may overlap in time, so no region has two owners:
+//   shared, written before the fork (prep launch, ray generation on the caller's stream), read-only after: every level's proj and
+//           rays, level 0's dv / nf of every cascade, every window's ray index / count;
+//   foreground sources (`side`): f_fg[0..2], featws_fg, tex_fg of every rendered level — read-only for the layers after `feats`;
+//   layer l (its lane stream): C[i][l].{dv, nf (i > 0), vol, feat3d, prob, depth, std, raw, z} of every level i, costreg_ws[l];
+//   background (caller's stream): f_bg[0..2], featws_bg, tex_bg, C[i][L].*, costreg_ws[L].
+// A layer's raw / z and the caller's outputs meet only in enerf_composite_layers, behind the join.
+// =====================================================================================================================
+constexpr int kCompCascades = ENERF_MAX_FG_LAYERS + 1;
+struct CompLevel {
+    int h, w, C, Hs, Ws, inv;              // volume grid, cost-volume channels, source-map size, depth_inv
+    int Hr, Wr, render, F, Ns, fl;         // render raster, flag, nerf feature width, samples per ray, texel feature level
+    int vwin[ENERF_MAX_FG_LAYERS][4];      // layer windows (x0, y0, ww, wh) of the volume grid ...
+    int rwin[ENERF_MAX_FG_LAYERS][4];      // ... and of the render raster
+    size_t proj, rays, tex_fg, tex_bg;
+};
+struct CompCascadeLevel {
+    int D, wh, ww, rows;                   // planes; the cost volume's extent (the window, or the grid); raw-render rows
+    size_t dv, nf, vol, feat3d, prob, depth, std, raw, z, index, count;
+    size_t costreg_bytes;
+};
+struct CompositePlan {
+    size_t f_fg[3], f_bg[3], featws_fg, featws_bg, featws_bytes;
+    CompLevel L[ENERF_MAX_LEVELS];
+    CompCascadeLevel C[ENERF_MAX_LEVELS][kCompCascades];
+    size_t costreg_ws[kCompCascades], costreg_ws_bytes[kCompCascades];
+    size_t total_floats;
+};
+// (bbox * scale).int() of network_composite.py:88 / utils.py:879: float32 product, truncation
+inline void scaled_box(const float* box, double scale, int* win) {
+    const float sc = (float)scale;
+    for (int k = 0; k < 4; ++k) { const volatile float v = box[k] * sc; win[k] = (int)v; }
+}
+int check_comp_window(const char* grid, int level, int l, const int* wn, int h, int w) {
+    REQUIRE(wn[2] > 0 && wn[3] > 0 && wn[0] >= 0 && wn[1] >= 0 && (long long)wn[0] + wn[2] <= w && (long long)wn[1] + wn[3] <= h,
+            "forward_composite: bbox[%d] at level %d is the window (x0 %d, y0 %d, %d x %d), outside the %d x %d %s", l, level, wn[0], wn[1],
+            wn[2], wn[3], w, h, grid);
+    return ENERF_OK;
+}
+
+int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P) {
+    REQUIRE(a, "forward_composite: null args");
+    const enerf_cascade_t& c = a->cas;
+    const int L = a->L;
+    REQUIRE(L >= 1 && L <= ENERF_MAX_FG_LAYERS, "forward_composite: L=%d foreground layers unsupported (1..%d)", L, ENERF_MAX_FG_LAYERS);
+    REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "forward_composite: cas.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
+    REQUIRE(a->S >= 2 && a->S <= 4 && a->H > 0 && a->W > 0 && a->H % 4 == 0 && a->W % 4 == 0,
+            "forward_composite: bad frame shape S=%d H=%d W=%d (S in 2..4, H and W divisible by 4)", a->S, a->H, a->W);
+    REQUIRE(a->src_inps && a->bg_src_inps, "forward_composite: src_inps / bg_src_inps is null");
+    REQUIRE(a->src_exts && a->src_ixts && a->tar_ext && a->tar_ixt, "forward_composite: src_exts / src_ixts / tar_ext / tar_ixt is null");
+    REQUIRE(a->near_far, "forward_composite: near_far is null");
+    REQUIRE(a->feature_net_packed && a->feature_net_bg_packed, "forward_composite: feature_net_packed / feature_net_bg_packed is null");
+    int covered = 0;
+    while (covered < ENERF_MAX_LEVELS && a->bg_volume_planes[covered] > 0) ++covered;
+    REQUIRE(c.num <= covered, "forward_composite: cas.num=%d levels but bg_volume_planes covers %d", c.num, covered);
+    for (int i = 0; i < c.num; ++i)
+        if (c.render_if[i]) {
+            REQUIRE(c.num_samples[i] >= 1 && L * c.num_samples[i] <= 16, "forward_composite: L * num_samples = %d * %d at level %d unsupported (at most 16)",
+                    L, c.num_samples[i], i);
+            REQUIRE(c.num_samples[i] <= 8, "forward_composite: cas.num_samples[%d]=%d unsupported (the render kernel takes 1..8 samples per ray)", i,
+                    c.num_samples[i]);
+        }
+    memset(P, 0, sizeof(*P));
+    size_t off = 0;
+    auto take = [&](size_t nfloats) { size_t r = off; off += (nfloats + 63) / 64 * 64; return r; };   // 256-B aligned
+    const FeatDims fd(a->H, a->W);
+    const int S = a->S;
+    for (int l = 0; l < 3; ++l) P->f_fg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+    for (int l = 0; l < 3; ++l) P->f_bg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+    P->featws_bytes = enerf_feature_net_workspace_bytes(S, a->H, a->W);
+    P->featws_fg = take(P->featws_bytes / sizeof(float));
+    P->featws_bg = take(P->featws_bytes / sizeof(float));
+    for (int i = 0; i < c.num; ++i) {
+        CompLevel& V = P->L[i];
+        V.h = scaled(a->H, c.volume_scale[i]);
+        V.w = scaled(a->W, c.volume_scale[i]);
+        V.C = fd.c[i]; V.Hs = fd.h[i]; V.Ws = fd.w[i]; V.inv = c.depth_inv[i];
+        REQUIRE(V.C == 16 || V.C == 32, "forward_composite: cas.num: level %d would warp %d-channel features (the windowed volume has 16 / 32)", i, V.C);
+        REQUIRE(V.h > 0 && V.w > 0 && V.h % 4 == 0 && V.w % 4 == 0,
+                "forward_composite: level %d volume grid h, w (%d, %d) of H, W (%d, %d) must be divisible by 4", i, V.h, V.w, a->H, a->W);
+        if (i > 0) REQUIRE(c.depth_inv[i - 1], "forward_composite: cas.depth_inv: cascade levels after a depth-space level are undefined in the "
+                                               "reference (utils.py:130)");
+        REQUIRE((long long)S * V.Hs * V.Ws * V.C < (1LL << 32) && (long long)V.Hs * V.Ws < (1LL << 23) && (long long)V.h * V.w < (1LL << 23),
+                "forward_composite: H, W: level %d too large for 32-bit gather offsets", i);
+        V.render = c.render_if[i] != 0;
+        V.proj = take((size_t)S * 12);
+        if (V.render) {
+            V.Hr = scaled(a->H, c.render_scale[i]);
+            V.Wr = scaled(a->W, c.render_scale[i]);
+            V.Ns = c.num_samples[i];
+            V.F = c.nerf_model_feat_ch[i] + 3;
+            REQUIRE(V.Hr > 1 && V.Wr > 1, "forward_composite: cas.render_scale: level %d render extent too small", i);
+            REQUIRE(V.F == 11 || V.F == 35, "forward_composite: cas.nerf_model_feat_ch[%d]=%d unsupported (8 or 32)", i, V.F - 3);
+            REQUIRE((long long)V.Hr * V.Wr * (L + 1) * V.Ns * 4 < (1LL << 31), "forward_composite: H, W: level %d render image too large", i);
+            {   // the raw render's own refusals (render.hip), asked here so that none is left for behind the fork
+                RenderArgs probe;
+                memset(&probe, 0, sizeof(probe));
+                probe.B = 1; probe.S = S; probe.N = V.Hr * V.Wr; probe.n_samples = V.Ns; probe.Hr = V.Hr; probe.Wr = V.Wr; probe.F = V.F;
+                probe.D = probe.h = probe.w = 1;                   // (vol = NULL: enerf_render_rays_raw passes ones)
+                const int code = render_rays_raw_check(probe);
+                REQUIRE(code != -5, "forward_composite: H, W: level %d render raster %d x %d with S=%d too large for the render kernel's 32-bit byte offsets",
+                        i, V.Wr, V.Hr, S);
+                REQUIRE(code == 0, "forward_composite: level %d render configuration unsupported (code %d: nerf_model_feat_ch=%d S=%d num_samples=%d)", i,
+                        code, V.F - 3, S, V.Ns);
+            }
+            if (int rc = check_render_feat("forward_composite", c, i, fd, V.Hr, V.Wr, true)) return rc;
+            V.fl = c.render_im_feat_level[i];
+            REQUIRE(a->rgb[i] && a->depth[i] && a->weights[i] && a->net_output[i] && a->z_vals[i],
+                    "forward_composite: level %d output (rgb / depth / weights / net_output / z_vals) is null", i);
+            REQUIRE((uintptr_t)a->net_output[i] % 16 == 0, "forward_composite: net_output[%d] must be 16-byte aligned", i);
+            if (a->rays[i] == nullptr) V.rays = take((size_t)V.Hr * V.Wr * 8);
+            V.tex_fg = take((size_t)S * V.Hr * V.Wr * tex_stride(V.F));
+            V.tex_bg = take((size_t)S * V.Hr * V.Wr * tex_stride(V.F));
+        }
+        for (int k = 0; k <= L; ++k) {
+            CompCascadeLevel& K = P->C[i][k];
+            const bool fg = k < L;
+            K.D = fg ? c.volume_planes[i] : a->bg_volume_planes[i];
+            REQUIRE(K.D > 0 && K.D % 4 == 0 && K.D <= 64, "forward_composite: %s[%d]=%d planes unsupported (divisible by 4, at most 64)",
+                    fg ? "cas.volume_planes" : "bg_volume_planes", i, K.D);
+            K.wh = V.h; K.ww = V.w; K.rows = V.render ? V.Hr * V.Wr : 0;
+            if (fg) {
+                scaled_box(a->bbox[k], c.volume_scale[i], V.vwin[k]);
+                if (int rc = check_comp_window("volume grid", i, k, V.vwin[k], V.h, V.w)) return rc;
+                K.ww = V.vwin[k][2]; K.wh = V.vwin[k][3];
+                REQUIRE(K.ww % 4 == 0 && K.wh % 4 == 0, "forward_composite: bbox[%d] at level %d is a %d x %d window: ww, wh must be divisible by 4",
+                        k, i, K.ww, K.wh);
+                if (V.render) {
+                    scaled_box(a->bbox[k], c.render_scale[i], V.rwin[k]);
+                    if (int rc = check_comp_window("ray raster", i, k, V.rwin[k], V.Hr, V.Wr)) return rc;
+                    K.rows = V.rwin[k][2] * V.rwin[k][3];
+                }
+            }
+            REQUIRE(a->cost_reg_packed[i][k], "forward_composite: cost_reg_packed[%d][%d] is null", i, k);
+            if (V.render) REQUIRE(a->nerf_packed[i][k], "forward_composite: nerf_packed[%d][%d] is null", i, k);
+            const size_t grid = (size_t)V.h * V.w, vox = (size_t)K.D * K.wh * K.ww;
+            REQUIRE((long long)K.D * V.h * V.w * (V.C / 4) < (1LL << 31) && (long long)K.D * V.h < (1LL << 23),
+                    "forward_composite: H, W: level %d volume too large for 32-bit voxel indices", i);
+            K.dv = take((size_t)K.D * grid);
+            K.nf = take(2 * grid);
+            K.vol = take(vox * V.C);
+            K.feat3d = take(vox * 8);
+            K.prob = take(vox);
+            if (a->depth_map[i][k] == nullptr) K.depth = take(grid);
+            if (a->std_map[i][k] == nullptr) K.std = take(grid);
+            if (V.render) {
+                K.raw = take((size_t)K.rows * V.Ns * 4);
+                K.z = take((size_t)K.rows * V.Ns);
+                if (fg) { K.index = take((size_t)K.rows); K.count = take(64); }
+            }
+            K.costreg_bytes = enerf_cost_reg_workspace_bytes(0, 1, K.D, K.wh, K.ww);
+            if (K.costreg_bytes > P->costreg_ws_bytes[k]) P->costreg_ws_bytes[k] = K.costreg_bytes;
+        }
+    }
+    for (int k = 0; k <= L; ++k) P->costreg_ws[k] = take(P->costreg_ws_bytes[k] / sizeof(float) + 1);
+    P->total_floats = off;
+    return ENERF_OK;
+}
+
+struct CompositeRun {
+    const enerf_composite_frame_args_t* a = nullptr;
+    CompositePlan P;
+    hipStream_t st = nullptr;            // the caller's stream
+    float* ws = nullptr;
+    int L = 0;
+    SideLane* lane = nullptr;
+    std::unique_lock<std::mutex> lane_busy;          // held until this call has enqueued its last join (side_lane.h)
+    bool forked = false;
+    bool dirty[kLaneStreams] = {false, false, false};     // the lane stream has launches the caller's stream has not waited for
+    // hand-off from level i - 1 to level i, per cascade
+    const float *pdepth[kCompCascades] = {}, *pstd[kCompCascades] = {}, *pnf[kCompCascades] = {};
+    int hp = 0, wp = 0;
+
+    const enerf_cascade_t& cas() const { return a->cas; }
+    LaneStream lane_of(int k) const { return !forked || k == L ? kLaneMain : (k & 1) ? kLaneRender : kLaneSide; }
+    LaneStream lane_of_sources() const { return forked ? kLaneSide : kLaneMain; }
+    hipStream_t on(LaneStream s) {       // the stream to enqueue on; a lane stream is un-joined from here on
+        if (s == kLaneMain) return st;
+        dirty[s] = true;
+        return lane->stream[s];
+    }
+    void join() {                        // the caller's stream waits for everything enqueued on the lane so far
+        if (dirty[kLaneSide]) { lane->record(kEvSideDone, kLaneSide); lane->wait(kLaneMain, kEvSideDone); dirty[kLaneSide] = false; }
+        if (dirty[kLaneRender]) { lane->record(kEvDone, kLaneRender); lane->wait(kLaneMain, kEvDone); dirty[kLaneRender] = false; }
+    }
+    // Error exit.  The plan repeats every refusal of the stage entries that depends on the arguments alone (shapes, windows, sample
+    // counts, the raw render's limits), so none of those is left for behind the fork, and the tests find none; what can still fail
+    // there is a launch error or a layer shape no convolution kernel takes.  Such an exit leaves through here: the caller's stream
+    // never returns ahead of a lane stream, whether or not that stream got a launch yet (FrameRun::bail's pattern).
+    int bail(int code) { join(); return code; }
+    int finish() { join(); return check_launch("forward_composite"); }
+    float* depth_of(int i, int k) const { return a->depth_map[i][k] ? a->depth_map[i][k] : ws + P.C[i][k].depth; }
+    float* std_of(int i, int k) const { return a->std_map[i][k] ? a->std_map[i][k] : ws + P.C[i][k].std; }
+    const float* rays_of(int i) const { return a->rays[i] ? a->rays[i] : ws + P.L[i].rays; }
+
+    // the plan, and everything the host can refuse before the first launch
+    int begin(const enerf_composite_frame_args_t* args, enerf_stream_t stream) {
+        a = args;
+        if (int rc = make_composite_plan(a, &P)) return rc;
+        REQUIRE(a->workspace, "forward_composite: workspace is null");
+        REQUIRE((uintptr_t)a->workspace % 16 == 0, "forward_composite: workspace must be 16-byte aligned");
+        if (a->workspace_bytes < P.total_floats * sizeof(float))
+            return fail(ENERF_EWORKSPACE, "forward_composite: workspace too small (%zu < %zu bytes)", a->workspace_bytes,
+                        P.total_floats * sizeof(float));
+        st = (hipStream_t)stream;
+        ws = (float*)a->workspace;
+        L = a->L;
+        return ENERF_OK;
+    }
+
+    // ---- everything that depends on the cameras, near_far and the boxes alone, on the caller's stream in front of the fork: the
+    // preparation launch (all proj, level 0's planes of every cascade, every window's ray list) and the generated rays
+    int prep() {
+        const enerf_cascade_t& c = cas();
+        enerf_composite_prep_t p;
+        memset(&p, 0, sizeof(p));
+        p.src_ixts = a->src_ixts; p.src_exts = a->src_exts; p.tar_ixt = a->tar_ixt; p.tar_ext = a->tar_ext; p.near_far = a->near_far;
+        p.L = L; p.S = a->S; p.num_levels = c.num;
+        p.fg_planes = P.C[0][0].D; p.bg_planes = P.C[0][L].D; p.h = P.L[0].h; p.w = P.L[0].w; p.depth_inv = c.depth_inv[0];
+        for (int k = 0; k <= L; ++k) { p.dv[k] = ws + P.C[0][k].dv; p.nf[k] = ws + P.C[0][k].nf; }
+        for (int i = 0; i < c.num; ++i) {
+            const CompLevel& V = P.L[i];
+            p.src_scale[i] = (float)c.im_feat_scale[i]; p.tar_scale[i] = (float)c.volume_scale[i]; p.proj[i] = ws + V.proj;
+            if (!V.render) continue;
+            p.Hr[i] = V.Hr; p.Wr[i] = V.Wr;
+            for (int l = 0; l < L; ++l) {
+                for (int q = 0; q < 4; ++q) p.win[i][l][q] = V.rwin[l][q];
+                p.index[i][l] = (int*)(ws + P.C[i][l].index); p.count[i][l] = (int*)(ws + P.C[i][l].count);
+            }
+        }
+        CompositePrep job;
+        if (int rc = composite_prep_job(&p, &job)) return rc;
+        launch_composite_prep(job, st);
+        if (int rc = check_launch("forward_composite: prep")) return rc;
+        for (int i = 0; i < c.num; ++i) {
+            const CompLevel& V = P.L[i];
+            if (!V.render || a->rays[i] != nullptr) continue;
+            if (int rc = enerf_gen_rays(a->tar_ext, a->tar_ixt, 1, V.Hr, V.Wr, (float)c.render_scale[i], ws + V.rays, st)) return rc;
+        }
+        return ENERF_OK;
+    }
+
+    // ---- the fork: the lane streams start behind the preparation (and with it behind whatever the caller's stream held before)
+    void fork() {
+        if (a->options && a->options->single_stream) return;
+        lane = side_lane(st);
+        if (lane == nullptr) return;
+        lane_busy = std::unique_lock<std::mutex>(lane->busy);
+        lane->record(kEvFork, kLaneMain);
+        lane->wait(kLaneSide, kEvFork);
+        dirty[kLaneSide] = true;                     // forked = to be joined, launches or not: an error exit in front of a stream's first
+        if (L >= 2) { lane->wait(kLaneRender, kEvFork); dirty[kLaneRender] = true; }      // launch must not leave it un-joined (stream capture)
+        forked = true;
+    }
+
+    // ---- sources: the two FeatureNets (feature_net.py:27-36, level_2 as plain features; both over src_inps) and every rendered level's
+    // texel images (the background's take their colours from bg_src_inps);
+    // the foreground's on the side stream, `feats` telling the render stream's layers they are there
+    int sources_of(const float* packed, const float* rgb, const size_t* f, size_t featws, bool fg, LaneStream s) {
+        const FeatDims fd(a->H, a->W);
+        const float* img = a->src_inps;              // BOTH nets read src_inps (network_composite.py:78-79); bg_src_inps only colours
+        if (int rc = feature_net_stage_job(packed, img, a->S, a->H, a->W, ws + f[0], ws + f[1], ws + f[2], 8, ws + featws, P.featws_bytes,
+                                           ENERF_FEAT_ALL, a->options, on(s), nullptr, nullptr))
+            return rc;
+        for (int i = 0; i < cas().num; ++i) {
+            const CompLevel& V = P.L[i];
+            if (!V.render) continue;
+            if (int rc = enerf_pack_texels_cl(ws + f[V.fl], fd.c[V.fl], rgb, a->H, a->W, V.Hr, V.Wr, tex_stride(V.F), a->S,
+                                              ws + (fg ? V.tex_fg : V.tex_bg), on(s)))
+                return rc;
+        }
+        return ENERF_OK;
+    }
+    int sources() {
+        int rc = sources_of(a->feature_net_packed, a->src_inps, P.f_fg, P.featws_fg, true, lane_of_sources());
+        if (forked && L >= 2) { lane->record(kEvFeats, kLaneSide); lane->wait(kLaneRender, kEvFeats); }
+        if (rc != ENERF_OK) return rc;
+        return sources_of(a->feature_net_bg_packed, a->bg_src_inps, P.f_bg, P.featws_bg, false, kLaneMain);
+    }
+
+    // ---- cascade k, level i, up to its depth / std maps (network_composite.py:83-113): depth planes (level 0's came with the
+    // preparation), the cost volume — of the layer's window only —, MinCostRegNet, the regression over the whole grid
+    int cascade_level(int i, int k) {
+        const CompLevel& V = P.L[i];
+        const CompCascadeLevel& K = P.C[i][k];
+        const bool fg = k < L;
+        hipStream_t s = on(lane_of(k));
+        float *dv = ws + K.dv, *nf = ws + K.nf, *vol = ws + K.vol, *prob = ws + K.prob, *depth = depth_of(i, k), *std = std_of(i, k);
+        const float* feat = ws + (fg ? P.f_fg : P.f_bg)[i];
+        const float* proj = ws + V.proj;
+        int rc = ENERF_OK;
+        if (i > 0)
+            rc = enerf_get_depth_values(a->near_far + 2 * k, pdepth[k], pstd[k], pnf[k], 1, K.D, V.h, V.w, hp, wp, V.inv, dv, nf, s);
+        if (rc != ENERF_OK) return rc;
+        const int* wn = V.vwin[k];
+        rc = fg ? enerf_build_feature_volume_window(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], vol, s)
+                : enerf_build_feature_volume(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, vol, s);
+        if (rc != ENERF_OK) return rc;
+        rc = cost_reg_run(a->cost_reg_packed[i][k], V.C, 0, vol, 0, 1, K.D, K.wh, K.ww, ws + K.feat3d, prob, ws + P.costreg_ws[k],
+                          P.costreg_ws_bytes[k], a->options, s);              // (feat3d: dead work)
+        if (rc != ENERF_OK) return rc;
+        rc = fg ? enerf_depth_regression_window(prob, dv, 1, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], V.inv, depth, std, s)
+                : enerf_depth_regression(prob, dv, 1, K.D, V.h, V.w, V.inv, depth, std, s);
+        pdepth[k] = depth; pstd[k] = std; pnf[k] = nf;
+        return rc;
+    }
+
+    // ---- cascade k, rendered level i: the raw samples of the layer's window (the background: of the whole raster) ----
+    int raw_render(int i, int k) {
+        const CompLevel& V = P.L[i];
+        const CompCascadeLevel& K = P.C[i][k];
+        const bool fg = k < L;
+        enerf_render_raw_args_t r;
+        memset(&r, 0, sizeof(r));
+        r.rays8 = rays_of(i); r.depth_map = pdepth[k]; r.std_map = pstd[k]; r.nf_map = pnf[k]; r.map_h = V.h; r.map_w = V.w;
+        r.tex = ws + (fg ? V.tex_fg : V.tex_bg); r.vol = nullptr;
+        r.src_exts = a->src_exts; r.src_ixts = a->src_ixts; r.tar_ext = a->tar_ext; r.packed = a->nerf_packed[i][k];
+        r.raw = ws + K.raw; r.z = ws + K.z;
+        r.B = 1; r.N = V.Hr * V.Wr; r.S = a->S; r.n_samples = V.Ns; r.depth_inv = V.inv; r.Hr = V.Hr; r.Wr = V.Wr; r.F = V.F;
+        r.render_scale = (float)cas().render_scale[i];
+        if (fg) { r.ray_index = (const int*)(ws + K.index); r.ray_count = (const int*)(ws + K.count); }
+        return enerf_render_rays_raw(&r, on(lane_of(k)));
+    }
+
+    // ---- rendered level i: parse_layer + raw2outputs_composite over the L layers' and the background's samples, behind the join ----
+    int merge(int i) {
+        const CompLevel& V = P.L[i];
+        join();
+        enerf_composite_layers_t m;
+        memset(&m, 0, sizeof(m));
+        for (int l = 0; l < L; ++l) {
+            m.fg_raw[l] = ws + P.C[i][l].raw; m.fg_z[l] = ws + P.C[i][l].z;
+            for (int q = 0; q < 4; ++q) m.win[l][q] = V.rwin[l][q];
+        }
+        m.bg_raw = ws + P.C[i][L].raw; m.bg_z = ws + P.C[i][L].z;
+        m.L = L; m.Ns = V.Ns; m.H = V.Hr; m.W = V.Wr; m.white_bkgd = 0;
+        m.rgb = a->rgb[i]; m.depth = a->depth[i]; m.weights = a->weights[i]; m.net_output = a->net_output[i]; m.z_vals = a->z_vals[i];
+        return enerf_composite_layers(&m, st);
+    }
+};
+
+int run_composite(const enerf_composite_frame_args_t* a, enerf_stream_t stream) {
+    CompositeRun R;
+    int rc = R.begin(a, stream);
+    if (rc != ENERF_OK) return rc;
+    rc = R.prep();
+    if (rc != ENERF_OK) return rc;                 // (nothing forked yet)
+    R.fork();
+    rc = R.sources();
+    if (rc != ENERF_OK) return R.bail(rc);
+    for (int i = 0; i < a->cas.num; ++i) {
+        const bool render = R.P.L[i].render != 0;
+        for (int k = 0; k <= a->L && rc == ENERF_OK; ++k) {       // the layers first: their lane streams get their work early
+            rc = R.cascade_level(i, k);
+            if (rc == ENERF_OK && render) rc = R.raw_render(i, k);
+        }
+        if (rc == ENERF_OK && render) rc = R.merge(i);
+        if (rc != ENERF_OK) return R.bail(rc);
+        R.hp = R.P.L[i].h; R.wp = R.P.L[i].w;
+    }
+    return R.finish();
+}
 }  // namespace
 }  // namespace enerf
 
@@ -830,5 +1208,14 @@ int enerf_source_cache_build(const enerf_source_cache_t* cache, const float* src
     launch_gather_sources(J, V, (hipStream_t)stream);
     return check_launch("source_cache_build");
 }
+
+// ---- the composite network in one call ----
+size_t enerf_forward_composite_workspace_bytes(const enerf_composite_frame_args_t* a) {
+    CompositePlan P;
+    if (make_composite_plan(a, &P) != ENERF_OK) return 0;
+    return P.total_floats * sizeof(float);
+}
+
+int enerf_forward_composite(const enerf_composite_frame_args_t* a, enerf_stream_t stream) { return run_composite(a, stream); }
 
 }  // extern "C"

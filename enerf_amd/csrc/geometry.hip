@@ -457,6 +457,18 @@ void launch_build_rays(const float* rays8, const float* depth, const float* std,
                         depth_inv, rays12);
 }
 
+// -------------------------------------------------------------------------------------------------
+// The composite network's camera-only preparation in one launch (prep_job.h, CompositePrep): every level's projection
+// matrices, level 0's depth planes of all 1 + L cascades, every rendered level's window ray indices.  A few hundred blocks,
+// no LDS; each output holds the bits k_proj_mats / k_depth_values / k_window_ray_index give it.
+// -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_composite_prep(CompositePrep J) {
+    composite_prep_block(J, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+}
+void launch_composite_prep(const CompositePrep& J, hipStream_t st) {
+    ENERF_LAUNCH_SIMPLE(k_composite_prep, (unsigned)J.nblocks, 256, 0, st, J);
+}
+
 }  // namespace enerf
 
 #include "composite_layers.h"      // the composite network's kernels (they share depth_moments_regs)

@@ -280,6 +280,7 @@ using RenderArgs = enerf_render_args_t;
 int launch_render_rays(const RenderArgs& a, hipStream_t st);  // returns 0, or <0 for unsupported shapes
 // the RAW instantiations: a.rgb = (n, Ns, 4) samples [r, g, b, sigma], a.depth = (n, Ns) metric sample depths, a.vol may be NULL
 int launch_render_rays_raw(const RenderArgs& a, hipStream_t st);
+int render_rays_raw_check(const RenderArgs& a);                // its refusals alone: 0 or the launcher's code, nothing launched
 
 // ---- the composite network (network_composite.py): volume.hip, composite_layers.h (included by geometry.hip) ----
 void launch_feature_volume_window(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs, int Ws, int D,
@@ -288,5 +289,10 @@ void launch_depth_regression_window(const float* prob, const float* dv, int B, i
                                     int depth_inv, float* depth, float* std, hipStream_t st);
 void launch_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* index, int* count, hipStream_t st);
 void launch_composite_layers(const enerf_composite_layers_t& a, hipStream_t st);
+// the composite frame's camera-only preparation (prep_job.h CompositePrep, geometry.hip k_composite_prep): composite_prep_job checks
+// the C arguments and lays the job out (ENERF_EINVAL + message, nothing launched), launch_composite_prep runs it
+struct CompositePrep;
+int composite_prep_job(const enerf_composite_prep_t* a, CompositePrep* job);
+void launch_composite_prep(const CompositePrep& job, hipStream_t st);
 
 }  // namespace enerf

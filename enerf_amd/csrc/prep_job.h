@@ -93,4 +93,61 @@ __device__ __forceinline__ void prep_job_block(const PrepJob& J, int vb, int tid
     depth_plane_value(J.near_far[b * 2 + 0], J.near_far[b * 2 + 1], b, k, p, J.D, hw, J.depth_inv, J.dv + i, J.nf);
 }
 
+// ---- the composite network's preparation (enerf_composite_prep, enerf_forward_composite): everything of a frame that depends on
+// the cameras, near_far and the boxes alone, in ONE launch at the head of the frame, before the layers' chains part:
+//   * every level's projection matrices (block 0, as above);
+//   * level 0's depth planes of all 1 + L cascades, each with its own near_far row and plane count (B == 1);
+//   * the ray index and count of every rendered level's L windows (k_window_ray_index's arithmetic).
+// One block-range per job, each at most kCompositePrepJobBlocks blocks whose threads stride over the job's elements: a few
+// hundred blocks in all whatever the image size.  No LDS, plain vector stores.  The device functions are the stand-alone
+// kernels' (proj_one, depth_plane_value): identical bits.
+constexpr int kCompositePrepCascades = 5;        // ENERF_MAX_FG_LAYERS + 1
+constexpr int kCompositePrepWindows = 12;        // ENERF_MAX_LEVELS * ENERF_MAX_FG_LAYERS
+constexpr int kCompositePrepJobBlocks = 32;
+struct CompositePrep {
+    ProjJob pj[3];                                // proj == nullptr: none
+    struct Planes { const float* near_far; float *dv, *nf; int D, block0, blocks; } cas[kCompositePrepCascades];
+    int n_cas, h, w, depth_inv;
+    struct Window { int x0, y0, ww, wh, Wr, block0, blocks; int *index, *count; } win[kCompositePrepWindows];
+    int n_win;
+    int nblocks;
+};
+inline int composite_prep_job_blocks(long long elements, int threads) {
+    const long long nb = (elements + threads - 1) / threads;
+    return (int)(nb < 1 ? 1 : nb > kCompositePrepJobBlocks ? kCompositePrepJobBlocks : nb);
+}
+__device__ __forceinline__ void composite_prep_block(const CompositePrep& J, int vb, int tid, int threads) {
+    if (vb == 0) {
+#pragma unroll 1
+        for (int l = 0; l < 3; ++l)
+            if (J.pj[l].proj != nullptr)
+                for (int q = tid; q < J.pj[l].S; q += threads)
+                    proj_one(q, J.pj[l].src_ixts, J.pj[l].src_exts, J.pj[l].tar_ixt, J.pj[l].tar_ext, J.pj[l].S, J.pj[l].src_scale,
+                             J.pj[l].tar_scale, J.pj[l].proj);
+    }
+    const int hw = J.h * J.w;
+#pragma unroll 1
+    for (int c = 0; c < J.n_cas; ++c) {
+        const CompositePrep::Planes& P = J.cas[c];
+        if (vb < P.block0 || vb >= P.block0 + P.blocks) continue;
+        const float nn = P.near_far[0], ff = P.near_far[1];
+        for (int i = (vb - P.block0) * threads + tid; i < P.D * hw; i += P.blocks * threads) {
+            const int k = i / hw, p = i - k * hw;
+            depth_plane_value(nn, ff, 0, k, p, P.D, hw, J.depth_inv, P.dv + i, P.nf);
+        }
+        return;
+    }
+#pragma unroll 1
+    for (int j = 0; j < J.n_win; ++j) {
+        const CompositePrep::Window& Wn = J.win[j];
+        if (vb < Wn.block0 || vb >= Wn.block0 + Wn.blocks) continue;
+        if (vb == Wn.block0 && tid == 0) Wn.count[0] = Wn.ww * Wn.wh;
+        for (int i = (vb - Wn.block0) * threads + tid; i < Wn.ww * Wn.wh; i += Wn.blocks * threads) {
+            const int yy = i / Wn.ww, xx = i - yy * Wn.ww;
+            Wn.index[i] = (Wn.y0 + yy) * Wn.Wr + Wn.x0 + xx;
+        }
+        return;
+    }
+}
+
 }  // namespace enerf

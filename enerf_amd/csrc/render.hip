@@ -915,13 +915,23 @@ int launch_render_rays(const RenderArgs& a, hipStream_t st) {
 // The RAW instantiations (see k_render_rays): a.rgb is the (n, Ns, 4) sample buffer, a.depth the (n, Ns) depths, a.vol may be
 // NULL.  One launch shape per F, the exact fp32 ones of the table above that hold any n_samples: 4-wave blocks x 2 per CU at
 // F = 11, one 8-wave block per CU at F = 35.
-int launch_render_rays_raw(const RenderArgs& a, hipStream_t st) {
+// every refusal of launch_render_rays_raw, from values alone (no launch, no HIP call): 0, or the launcher's code.  The composite
+// frame's plan asks before its first launch (frame.hip make_composite_plan), the launcher itself before it launches.
+int render_rays_raw_check(const RenderArgs& a) {
     if (a.n_samples < 1 || a.n_samples > 8) return -1;
     const int R = (a.F + 3) / 4;
     if ((long long)a.B * a.S * a.Hr * a.Wr * 4 * R >= (1LL << 30) || (long long)a.B * a.D * a.h * a.w * 8 >= (1LL << 30) ||
         (long long)a.Hr * a.Wr >= (1LL << 23) || (long long)a.h * a.w >= (1LL << 23) || a.D >= (1 << 23))
         return -5;
     if (nerf_layout(a.F).total > (R == 3 ? 10560 : 14528)) return -6;
+    if (R != 3 && R != 9) return -4;
+    if (R == 3 ? render_shmem<3, ENERF_RENDER_WAVES>(a) > 160 * 1024 / ENERF_RENDER_OCC : render_shmem<9, 8>(a) > 160 * 1024) return -2;
+    if (a.S < 2 || a.S > 4) return -3;
+    return 0;
+}
+int launch_render_rays_raw(const RenderArgs& a, hipStream_t st) {
+    if (const int rc = render_rays_raw_check(a)) return rc;
+    const int R = (a.F + 3) / 4;
     const long long ntiles = cdivl((long long)a.B * a.N, 16);
     const int cus = device_cu_count();
     auto grid_for = [&](int waves, int occ) {

@@ -9,6 +9,15 @@
 // training-style eval) is a leaf as well — nothing in the next level reads its rgb/depth/weights — so it is forked onto the
 // `render` stream after the level's depth regression and joined at the end of the frame.
 //
+// The composite network's frame (enerf_forward_composite, frame.hip CompositeRun) uses the same three streams differently: its
+// 1 + L cascades read nothing of each other until a rendered level's layer merge, and the foreground and background chains are
+// about equally long.  The caller's stream carries feature_net_bg and the background cascade; everything foreground is forked
+// behind the frame's preparation launch (`fork`): feature_net and the texel packs of src_inps on `side` (`feats` tells `render`
+// they are done), then layer l's cascade and raw renders on `side` for even l, on `render` for odd l — one layer per stream at
+// L = 2, and never more streams than these three (a process here has four hardware queues).  In front of each rendered level's
+// enerf_composite_layers, and at the end of the call, the caller's stream waits for `sidedone` / `done`, recorded behind the
+// last launch of `side` / `render`.
+//
 // The driver speaks two verbs only: record(event, stream) and wait(stream, event), over named streams and events.
 // One lane per (device, caller stream), created on first use, never destroyed (process lifetime).  Two implementations:
 //   * HIP: lowest-priority non-blocking streams and timing-free events;
@@ -26,7 +35,7 @@ namespace enerf {
 namespace {        // internal linkage: the lane is the frame driver's alone and adds nothing to the library's symbols
 
 enum LaneStream { kLaneMain = 0, kLaneSide, kLaneRender, kLaneStreams };        // main: the caller's stream
-enum LaneEvent { kEvTrunk = 0, kEvL1, kEvL2, kEvFork, kEvDone, kLaneEvents };
+enum LaneEvent { kEvTrunk = 0, kEvL1, kEvL2, kEvFork, kEvDone, kEvFeats, kEvSideDone, kLaneEvents };
 
 struct SideLane {
     hipStream_t stream[kLaneStreams];
@@ -63,7 +72,7 @@ struct SideLane {
     static int device() { return 0; }
 #ifdef ENERF_EMU_TRACE                             // (hip_emu.h has the trace; without it the verbs do nothing)
     static const char* name(LaneStream s) { static const char* n[] = {"main", "side", "render"}; return n[s]; }
-    static const char* name(LaneEvent e) { static const char* n[] = {"trunk", "l1", "l2", "fork", "done"}; return n[e]; }
+    static const char* name(LaneEvent e) { static const char* n[] = {"trunk", "l1", "l2", "fork", "done", "feats", "sidedone"}; return n[e]; }
     void record(LaneEvent e, LaneStream on) { emu::trace_sync("record", name(e), name(on), stream[on]); }
     void wait(LaneStream who, LaneEvent e) { emu::trace_sync("wait", name(e), name(who), stream[who]); }
 #else

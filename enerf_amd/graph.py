@@ -26,6 +26,14 @@ class GraphedFrame:
             raise RuntimeError("GraphedFrame: call net.eval() first")
         if getattr(net, "human", False) and not net.static_shapes:
             raise RuntimeError("GraphedFrame: the human variant needs static_shapes=True (no count readback inside a graph)")
+        # the composite network (network_composite.py) reads its boxes on the host: a device tensor would be a readback inside the
+        # capture, and the boxes' windows are baked into the captured launches
+        self.composite = hasattr(net, "num_fg_layers")
+        if self.composite:
+            if torch.is_tensor(batch.get("bbox")) and batch["bbox"].is_cuda:
+                raise RuntimeError("GraphedFrame: the composite network needs batch['bbox'] on the host (a CPU tensor or a sequence); "
+                                   "a device tensor is a readback inside the capture")
+            self._boxes = net._boxes(batch)
         self.net = net
         # kept for the life of the graph: the closure owns what the captured kernels read besides the network's own buffers
         # (a SourceCache's maps live outside the graph's private pool)
@@ -46,15 +54,21 @@ class GraphedFrame:
                 self.static_out = run(self.static_in)
         # the graph holds raw addresses of the packed weight images and the FeatureNet scratch, which live OUTSIDE the
         # graph's private pool: keep them alive here and refuse to replay once the network has replaced them
-        self._held = {k: v[0] for k, v in net._packed.items()}
-        self._held_ws = {k: v["ws"] for k, v in net._frames.items()}     # the frame workspaces
+        if self.composite:               # its packed images are plain tensors, its per-shape buffers hold the frame's workspace
+            self._held = dict(net._packed)
+            self._held_ws = {k: dict(v) for k, v in net._shapes.items()}
+        else:
+            self._held = {k: v[0] for k, v in net._packed.items()}
+            self._held_ws = {k: v["ws"] for k, v in net._frames.items()}     # the frame workspaces
 
     def __call__(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         for k, t in self._held.items():
             ent = self.net._packed.get(k)
-            if ent is None or ent[0] is not t:
+            if ent is None or (ent if self.composite else ent[0]) is not t:
                 raise RuntimeError("GraphedFrame: the network's weights changed (load_state_dict / .to()) after capture; "
                                    "re-capture the frame")
+        if self.composite and self.net._boxes(batch) != self._boxes:
+            raise RuntimeError("GraphedFrame: batch['bbox'] changed; the boxes' windows are part of the captured launches: re-capture")
         for k, v in batch.items():
             if torch.is_tensor(v):
                 dst = self.static_in[k]

@@ -137,6 +137,30 @@ class FrameArgs(C.Structure):
                    ("stage_events", C.POINTER(C.c_void_p))])
 
 
+_CASC = MAX_FG_LAYERS + 1           # cascades of a composite frame: the foreground layers, then the background
+
+
+class CompositePrepArgs(C.Structure):
+    """``enerf_composite_prep_t``."""
+    _fields_ = ([(n, _f) for n in ("src_ixts", "src_exts", "tar_ixt", "tar_ext", "near_far")] + [("L", _i), ("S", _i), ("num_levels", _i)]
+                + [("src_scale", _fl * MAX_LEVELS), ("tar_scale", _fl * MAX_LEVELS), ("proj", _fL)]
+                + [(n, _i) for n in ("fg_planes", "bg_planes", "h", "w", "depth_inv")]
+                + [("dv", C.c_void_p * _CASC), ("nf", C.c_void_p * _CASC), ("Hr", _iL), ("Wr", _iL),
+                   ("win", ((_i * 4) * MAX_FG_LAYERS) * MAX_LEVELS), ("index", (C.c_void_p * MAX_FG_LAYERS) * MAX_LEVELS),
+                   ("count", (C.c_void_p * MAX_FG_LAYERS) * MAX_LEVELS)])
+
+
+class CompositeFrameArgs(C.Structure):
+    """``enerf_composite_frame_args_t``."""
+    _fields_ = ([(n, _f) for n in ("src_inps", "bg_src_inps", "src_exts", "src_ixts", "tar_ext", "tar_ixt", "near_far")]
+                + [("bbox", (_fl * 4) * MAX_FG_LAYERS)] + [(n, _i) for n in ("L", "S", "H", "W")] + [("cas", Cascade)]
+                + [("bg_volume_planes", _iL), ("rays", _fL), ("feature_net_packed", _f), ("feature_net_bg_packed", _f),
+                   ("cost_reg_packed", (C.c_void_p * _CASC) * MAX_LEVELS), ("nerf_packed", (C.c_void_p * _CASC) * MAX_LEVELS)]
+                + [(n, _fL) for n in ("rgb", "depth", "weights", "net_output", "z_vals")]
+                + [("depth_map", (C.c_void_p * _CASC) * MAX_LEVELS), ("std_map", (C.c_void_p * _CASC) * MAX_LEVELS),
+                   ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("options", C.POINTER(Options))])
+
+
 class SourceCacheStruct(C.Structure):
     """``enerf_source_cache_t``."""
     _fields_ = ([(n, _f) for n in ("feat_l0", "feat_l1", "feat_l2")] + [("tex", _fL), ("exts", _f), ("ixts", _f)]
@@ -312,6 +336,9 @@ _SIGNATURES = {
     "enerf_window_ray_index": (_i, [_i] * 6 + [C.c_void_p, C.c_void_p, _f]),
     "enerf_render_rays_raw": (_i, [C.POINTER(RenderRawArgs), _f]),
     "enerf_composite_layers": (_i, [C.POINTER(CompositeLayersArgs), _f]),
+    "enerf_composite_prep": (_i, [C.POINTER(CompositePrepArgs), _f]),
+    "enerf_forward_composite_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs)]),
+    "enerf_forward_composite": (_i, [C.POINTER(CompositeFrameArgs), _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -725,6 +752,52 @@ class EnerfLib:
         self._check(self.dll.enerf_composite_layers(C.byref(a), self.stream_of(bg_z)), "composite_layers")
         return res
 
+    def composite_prep(self, src_ixts, src_exts, tar_ixt, tar_ext, near_far, scales, fg_planes, bg_planes, h, w, depth_inv, rasters,
+                       windows):
+        """The composite frame's camera-only preparation in one launch.  ``near_far`` (L+1, 2), the background's row last;
+        ``scales`` = [(src_scale, tar_scale)] per level; ``rasters`` = [(Hr, Wr) or None] per level; ``windows[i]`` = the L windows
+        (x0, y0, ww, wh) of level i's raster (ignored where the raster is None).  Returns ``(proj, dv, nf, index)``: proj[i]
+        (1,S,3,4) per level; dv[c] (1,D_c,h,w), nf[c] (1,2,h,w) per cascade; index[i] = [(index, count)] per window, or None."""
+        dev = src_ixts.device
+        S = int(src_ixts.shape[1])
+        L = int(near_far.shape[0]) - 1
+        if not 1 <= L <= MAX_FG_LAYERS or len(scales) > MAX_LEVELS:
+            raise EnerfError(f"composite_prep: L={L} layers (1..{MAX_FG_LAYERS}), {len(scales)} levels (at most {MAX_LEVELS})")
+        a = CompositePrepArgs(L=L, S=S, num_levels=len(scales), fg_planes=int(fg_planes), bg_planes=int(bg_planes), h=int(h), w=int(w),
+                              depth_inv=int(depth_inv))
+        a.src_ixts, a.src_exts, a.tar_ixt, a.tar_ext, a.near_far = (_ptr(t) for t in (src_ixts, src_exts, tar_ixt, tar_ext, near_far))
+        proj, dv, nf, index = [], [], [], []
+        for i, (ss, ts) in enumerate(scales):
+            a.src_scale[i], a.tar_scale[i] = float(ss), float(ts)
+            proj.append(torch.empty((1, S, 3, 4), dtype=torch.float32, device=dev))
+            a.proj[i] = proj[-1].data_ptr()
+            index.append(None)
+            if rasters[i] is None:
+                continue
+            a.Hr[i], a.Wr[i] = int(rasters[i][0]), int(rasters[i][1])
+            index[i] = []
+            for l in range(L):
+                x0, y0, ww, wh = (int(v) for v in windows[i][l])
+                pair = (torch.empty((max(ww * wh, 1),), dtype=torch.int32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+                index[i].append(pair)
+                a.win[i][l][0], a.win[i][l][1], a.win[i][l][2], a.win[i][l][3] = x0, y0, ww, wh
+                a.index[i][l], a.count[i][l] = pair[0].data_ptr(), pair[1].data_ptr()
+        for c in range(L + 1):
+            D = int(fg_planes) if c < L else int(bg_planes)
+            dv.append(torch.empty((1, max(D, 0), max(int(h), 0), max(int(w), 0)), dtype=torch.float32, device=dev))
+            nf.append(torch.empty((1, 2, max(int(h), 0), max(int(w), 0)), dtype=torch.float32, device=dev))
+            a.dv[c], a.nf[c] = dv[-1].data_ptr(), nf[-1].data_ptr()
+        self._check(self.dll.enerf_composite_prep(C.byref(a), self.stream_of(src_ixts)), "composite_prep")
+        return proj, dv, nf, index
+
+    def forward_composite_workspace_bytes(self, args: "CompositeFrameArgs") -> int:
+        n = self.dll.enerf_forward_composite_workspace_bytes(C.byref(args))
+        if n == 0:
+            raise EnerfError(f"forward_composite: {self.dll.enerf_last_error().decode()}")
+        return n
+
+    def forward_composite(self, args: "CompositeFrameArgs", stream):
+        self._check(self.dll.enerf_forward_composite(C.byref(args), stream), "forward_composite")
 
     # -- backward kernels (training path; wrapped by enerf_amd/autograd.py) -----------------------------
     def build_feature_volume_bwd(self, feat_cl, proj, dv, grad_vol):

@@ -12,6 +12,11 @@ modules only own parameters; everything runs in the library's HIP kernels (inclu
     and the kernel stops at the MLP (``enerf_render_rays_raw``);
   * ``enerf_composite_layers`` is parse_layer + raw2outputs_composite, one thread per pixel.
 
+A frame is ONE C call, ``enerf_forward_composite`` (csrc/frame.hip): the driver runs the stages above itself, the foreground layers
+forked onto the library's side lane (``options.single_stream`` keeps the frame on the caller's stream).  ``Network(...,
+driver="staged")`` keeps the earlier path — one ctypes call per stage, the same kernels, the same bits — and a ``stage_hook`` selects
+it for that frame too (per-stage timing, tools/time_composite.py).
+
 Restrictions, all stated in DESIGN.md §8: inference only (``forward`` raises in training mode); ``B == 1`` (the reference reads
 ``batch['bbox'][0]`` for every batch element); ``feature_backend="hip"``; no source cache, ``SequencePlayer`` or multi-GPU
 driver; at most four foreground layers with ``num_fg_layers * num_samples <= 16`` per level.
@@ -32,11 +37,13 @@ from __future__ import annotations
 from collections import OrderedDict
 from typing import Dict, Optional
 
+import ctypes as C
+
 import torch
 import torch.nn as nn
 
 from .config import EnerfConfig
-from .lib import MAX_FG_LAYERS, EnerfLib, NerfRaw, Options, get_lib
+from .lib import MAX_FG_LAYERS, CompositeFrameArgs, EnerfLib, NerfRaw, Options, cascade_struct, get_lib
 from .network import AggParams, CostRegParams, FeatureNet, _fc, _kaiming, _require_f32c
 
 BG_PLANES = (16, 4)          # network_composite.py:122: the background's depth planes per level
@@ -88,10 +95,13 @@ class Network(nn.Module):
     """ENeRF-Outdoor's layered renderer with the reference's call surface (network_composite.py:11-146)."""
 
     def __init__(self, cfg: Optional[EnerfConfig] = None, num_fg_layers: int = 1, lib: Optional[EnerfLib] = None,
-                 feature_backend: str = "hip"):
+                 feature_backend: str = "hip", driver: str = "call"):
         super().__init__()
         if feature_backend != "hip":
             raise ValueError("network_composite: feature_backend must be 'hip'")
+        if driver not in ("call", "staged"):
+            raise ValueError("network_composite: driver must be 'call' (enerf_forward_composite) or 'staged' (one C call per stage)")
+        self.driver = driver
         if not 1 <= int(num_fg_layers) <= MAX_FG_LAYERS:
             raise ValueError(f"network_composite: num_fg_layers must be in 1..{MAX_FG_LAYERS}")
         self.cfg = cfg or EnerfConfig(viewdir_agg=False).with_cas(volume_planes=(32, 8), num_samples=(2, 1))      # actor1.yaml
@@ -112,7 +122,7 @@ class Network(nn.Module):
             setattr(self, f"cost_reg_{i}_bg", CostRegParams(int(32 * (2 ** (-i))), full=False))
             setattr(self, f"nerf_{i}_bg", NerfCompositeParams(cas.nerf_model_feat_ch[i] + 3, self.cfg.viewdir_agg))
         self._packed: Dict[str, torch.Tensor] = {}
-        self._buffers: "OrderedDict[tuple, dict]" = OrderedDict()     # frame shape -> its buffers (_shape_buffers)
+        self._shapes: "OrderedDict[tuple, dict]" = OrderedDict()     # frame shape -> its buffers (_shape_buffers)
         self.intermediates: Dict[str, torch.Tensor] = {}
         self.stage_hook = None                         # optional callable(stage name), called between the stages of forward()
 
@@ -125,7 +135,7 @@ class Network(nn.Module):
 
     def invalidate_packed(self):
         self._packed = {}
-        self._buffers = OrderedDict()
+        self._shapes = OrderedDict()
 
     def _apply(self, fn, *a, **k):
         self.invalidate_packed()
@@ -176,14 +186,14 @@ class Network(nn.Module):
     def _shape_buffers(self, key):
         """The buffers of one frame shape — (H, W, S, boxes, device) — allocated on the first frame of that shape and reused by every
         later one; the few most recent shapes are kept (moving boxes change the windowed buffers' sizes)."""
-        st = self._buffers.get(key)
+        st = self._shapes.get(key)
         if st is None:
             st = {}
-            while len(self._buffers) >= MAX_SHAPES:
-                self._buffers.popitem(last=False)
-            self._buffers[key] = st
+            while len(self._shapes) >= MAX_SHAPES:
+                self._shapes.popitem(last=False)
+            self._shapes[key] = st
         else:
-            self._buffers.move_to_end(key)
+            self._shapes.move_to_end(key)
         dev = key[-1]
 
         def buf(name, shape, dtype=torch.float32):
@@ -236,6 +246,8 @@ class Network(nn.Module):
         bg4 = held("bg_src_inps", batch["bg_src_inps"], (S, 3, H, W))
         nfs = buf("near_far", (L + 1, 1, 2))                        # one contiguous (1, 2) range per cascade
         nfs.copy_(near_far.reshape(L + 1, 1, 2))
+        if self.driver == "call" and self.stage_hook is None:
+            return self._forward_call(batch, st, buf, held, boxes, (src4, bg4, exts, ixts, tar_ext, tar_ixt, nfs), S, H, W)
         hook("begin")
         feats, feats_bg = [], []
         for name, into in (("feature_net", feats), ("feature_net_bg", feats_bg)):           # both read src_inps (network_composite.py:78-79)
@@ -318,3 +330,59 @@ class Network(nn.Module):
             hook(f"level{i}_background" + ("+composite" if render else ""))
         self.intermediates = inter
         return ret
+
+    def _forward_call(self, batch, st, buf, held, boxes, inputs, S, H, W):
+        """The frame as ONE C call (enerf_forward_composite): the shape's outputs, depth / std maps and one workspace tensor are handed
+        to the driver, which runs the stages of the staged path below ``forward`` itself — same kernels, same bits — with the
+        foreground layers forked onto the library's side lane unless ``options.single_stream``."""
+        cas, lib, L = self.cfg.cas, self.lib, self.num_fg_layers
+        whos = [f"layer{l}" for l in range(L)] + ["bg"]
+        a = st.get("call.args")
+        if a is None:                                   # everything that belongs to the shape: filled once
+            a = CompositeFrameArgs(L=L, S=S, H=H, W=W, cas=cascade_struct(self.cfg))
+            for l, box in enumerate(boxes):
+                for k in range(4):
+                    a.bbox[l][k] = float(box[k])
+            a.feature_net_packed = self._packed_weights("feature_net").data_ptr()
+            a.feature_net_bg_packed = self._packed_weights("feature_net_bg").data_ptr()
+            outs, inter = {}, {}
+            for i in range(cas.num):
+                a.bg_volume_planes[i] = BG_PLANES[i]
+                h, w = int(H * cas.volume_scale[i]), int(W * cas.volume_scale[i])
+                Hr, Wr = int(H * cas.render_scale[i]), int(W * cas.render_scale[i])
+                for c, who in enumerate(whos):
+                    a.cost_reg_packed[i][c] = self._packed_weights(f"cost_reg_{i}_{who}").data_ptr()
+                    maps = (buf(f"{who}.{i}.depth", (1, h, w)), buf(f"{who}.{i}.std", (1, h, w)))
+                    a.depth_map[i][c], a.std_map[i][c] = maps[0].data_ptr(), maps[1].data_ptr()
+                    inter[f"depth_{i}_{who}"], inter[f"std_{i}_{who}"] = maps
+                    if cas.render_if[i]:
+                        a.nerf_packed[i][c] = self._packed_weights(f"nerf_{i}_{who}").data_ptr()
+                if cas.render_if[i]:
+                    N, Ns = Hr * Wr, cas.num_samples[i]
+                    T = (L + 1) * Ns
+                    out = {"rgb": buf(f"out{i}.rgb", (N, 3)), "depth": buf(f"out{i}.depth", (N,)), "weights": buf(f"out{i}.weights", (N, T)),
+                           "net_output": buf(f"out{i}.net_output", (N, T, 4)), "z_vals": buf(f"out{i}.z_vals", (N, L * Ns))}
+                    for k, v in out.items():
+                        getattr(a, k)[i] = v.data_ptr()
+                    outs.update({f"{k}_level{i}": v.unsqueeze(0) for k, v in out.items()})
+            st["call.outs"], st["call.inter"] = outs, inter
+        src4, bg4, exts, ixts, tar_ext, tar_ixt, nfs = inputs
+        a.src_inps, a.bg_src_inps, a.src_exts, a.src_ixts = src4.data_ptr(), bg4.data_ptr(), exts.data_ptr(), ixts.data_ptr()
+        a.tar_ext, a.tar_ixt, a.near_far = tar_ext.data_ptr(), tar_ixt.data_ptr(), nfs.data_ptr()
+        for i in range(cas.num):
+            rays = batch.get(f"rays_{i}") if cas.render_if[i] else None
+            if rays is not None:
+                n = int(H * cas.render_scale[i]) * int(W * cas.render_scale[i])
+                if tuple(rays.shape) != (1, n, 8):
+                    raise ValueError(f"network_composite: rays_{i} must be the full (1, {n}, 8) raster of the level")
+                rays = held(f"rays{i}", rays, (1, n, 8))
+            a.rays[i] = None if rays is None else rays.data_ptr()
+        opts = self.options                              # (kept alive by self for the length of the call)
+        a.options = None if opts is None else C.pointer(opts)
+        if "call.args" not in st:                        # one workspace per shape, sized by the plan (which refuses a bad frame here)
+            ws = buf("call.ws", ((lib.forward_composite_workspace_bytes(a) + 3) // 4,))
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+            st["call.args"] = a
+        lib.forward_composite(a, lib.stream_of(src4))
+        self.intermediates = dict(st["call.inter"])
+        return dict(st["call.outs"])

@@ -858,6 +858,80 @@ typedef struct {
 } enerf_composite_layers_t;
 int enerf_composite_layers(const enerf_composite_layers_t* args, enerf_stream_t stream);
 
+/* ---- the composite network in one call (ABI v11 grew by these three entries; new symbols only, the version number is unchanged) ----
+ * B == 1 throughout.  Cascade c = 0 .. L-1 is foreground layer c, cascade L the background ("background last").
+ *   enerf_composite_prep    everything of a composite frame that depends on the cameras, near_far and the boxes alone, in ONE launch:
+ *       proj[i] (1,S,3,4), i < num_levels = enerf_get_proj_mats(src_scale[i], tar_scale[i]); level 0's depth planes of all 1 + L
+ *       cascades, dv[c] (1,D_c,h,w) and nf[c] (1,2,h,w) = enerf_get_depth_values(near_far + 2c, no previous level), D_c = fg_planes,
+ *       the background's bg_planes; for every level with Hr[i] > 0 the L windows' ray lists, index[i][l] (>= ww*wh) and count[i][l]
+ *       (1) = enerf_window_ray_index(win[i][l], Hr[i], Wr[i]).  Every output holds the bits of those three entries.
+ *       ENERF_EINVAL, nothing launched: a null pointer, L outside 1..ENERF_MAX_FG_LAYERS, S < 1, num_levels outside 1..ENERF_MAX_LEVELS,
+ *       planes / h / w < 1, a window outside its raster.
+ *   enerf_forward_composite Network.forward of network_composite.py:77-146 as one call: the two FeatureNets, the 1 + L cascades, their
+ *       raw renders and enerf_composite_layers per rendered level — per cascade and level exactly the kernels of the separate entries
+ *       above (the windowed volume / regression for a layer, enerf_cost_reg on a channels-last volume, enerf_render_rays_raw with
+ *       vol = NULL), so every output and every depth / std map is bit-identical to calling them one by one; only
+ *       enerf_composite_prep's launch replaces theirs.  It only enqueues: no synchronisation, no allocation.
+ *       Streams: unless options->single_stream, the foreground work (feature_net, the texel packs of src_inps, the L layer
+ *       cascades and their raw renders) is forked off the caller's stream onto the frame's side lane (two library-owned streams)
+ *       and joined in front of each rendered level's enerf_composite_layers and at the end of the call, also when it fails;
+ *       the caller's stream carries feature_net_bg and the background cascade.  Chains that can overlap share no scratch:
+ *       enerf_forward_composite_workspace_bytes sizes one FeatureNet workspace per net and one set of volume / cost-reg /
+ *       sample regions per cascade.
+ *       bbox[l] = (x, y, w, h) of layer l in pixels of the input image; per level the window is the box times the level's
+ *       volume_scale (cost volume) or render_scale (rays): float32 product, then truncation, as the reference's
+ *       (bbox * scale).int().  cas.volume_planes are the foreground's planes, bg_volume_planes the background's.
+ *       rays[i] (1,Hr*Wr,8): the FULL raster of rendered level i, or NULL = generated on the device (workspace).
+ *       Outputs per rendered level i, N = Hr*Wr, Ns = cas.num_samples[i], T = (L+1)*Ns: rgb (N,3), depth (N), weights (N,T),
+ *       net_output (N,T,4), z_vals (N,L*Ns) as enerf_composite_layers writes them (white_bkgd off).  depth_map[i][c] / std_map[i][c]
+ *       (1,h_i,w_i), optional: cascade c's regressed maps of level i; NULL = kept in the workspace.
+ *       Refused before anything is launched (ENERF_EINVAL and a message naming the field; a workspace that is too small:
+ *       ENERF_EWORKSPACE): null pointers, L outside 1..4, L * num_samples > 16, S outside 2..4, H or W not divisible by 4,
+ *       cas.num beyond the levels bg_volume_planes covers, a window outside its grid, a window's ww / wh, a level's h / w or a
+ *       plane count not divisible by 4, render_im_feat_level not naming the feature map at the render resolution, a workspace that is
+ *       not 16-byte aligned.  enerf_forward_composite_workspace_bytes returns 0 for the same (see enerf_last_error). */
+typedef struct {
+    const float *src_ixts, *src_exts, *tar_ixt, *tar_ext; /* (1,S,3,3), (1,S,4,4), (1,3,3), (1,4,4) */
+    const float* near_far;                                 /* (L+1,2), the background's row last */
+    int L, S, num_levels;
+    float src_scale[ENERF_MAX_LEVELS], tar_scale[ENERF_MAX_LEVELS]; /* im_feat_scale, volume_scale of the level */
+    float* proj[ENERF_MAX_LEVELS];
+    int fg_planes, bg_planes, h, w, depth_inv;             /* level 0 */
+    float* dv[ENERF_MAX_FG_LAYERS + 1];
+    float* nf[ENERF_MAX_FG_LAYERS + 1];
+    int Hr[ENERF_MAX_LEVELS], Wr[ENERF_MAX_LEVELS];        /* the level's ray raster; Hr == 0: no windows at this level */
+    int win[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS][4];     /* x0, y0, ww, wh in the (Hr, Wr) raster */
+    int* index[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS];
+    int* count[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS];
+} enerf_composite_prep_t;
+int enerf_composite_prep(const enerf_composite_prep_t* args, enerf_stream_t stream);
+typedef struct {
+    const float *src_inps, *bg_src_inps;       /* (S,3,H,W) in [-1,1]: both FeatureNets read src_inps (network_composite.py:78-79);
+                                                  bg_src_inps gives the background's texels their colours */
+    const float *src_exts, *src_ixts, *tar_ext, *tar_ixt;
+    const float* near_far;                     /* (L+1,2), the background's row last */
+    float bbox[ENERF_MAX_FG_LAYERS][4];        /* (x, y, w, h) in pixels of the input image */
+    int L, S, H, W;
+    enerf_cascade_t cas;                       /* volume_planes: the foreground layers' */
+    int bg_volume_planes[ENERF_MAX_LEVELS];    /* the background's (network_composite.py:122: 16, 4); 0 = level not covered */
+    const float* rays[ENERF_MAX_LEVELS];
+    const float *feature_net_packed, *feature_net_bg_packed;
+    const float* cost_reg_packed[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS + 1]; /* [level][cascade], the background's at index L */
+    const float* nerf_packed[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS + 1];     /* rendered levels only */
+    float* rgb[ENERF_MAX_LEVELS];
+    float* depth[ENERF_MAX_LEVELS];
+    float* weights[ENERF_MAX_LEVELS];
+    float* net_output[ENERF_MAX_LEVELS];
+    float* z_vals[ENERF_MAX_LEVELS];
+    float* depth_map[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS + 1];
+    float* std_map[ENERF_MAX_LEVELS][ENERF_MAX_FG_LAYERS + 1];
+    void* workspace;
+    size_t workspace_bytes;
+    const enerf_options_t* options;
+} enerf_composite_frame_args_t;
+size_t enerf_forward_composite_workspace_bytes(const enerf_composite_frame_args_t* args);
+int enerf_forward_composite(const enerf_composite_frame_args_t* args, enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
