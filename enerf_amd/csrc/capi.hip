@@ -470,6 +470,11 @@ int enerf_render_rays_raw(const enerf_render_raw_args_t* a, enerf_stream_t strea
     return check_launch("render_rays_raw");
 }
 int enerf_composite_layers(const enerf_composite_layers_t* a, enerf_stream_t stream) {
+    return enerf::composite_layers_run(a, nullptr, (hipStream_t)stream);
+}
+}  // extern "C"
+namespace enerf {
+int composite_layers_run(const enerf_composite_layers_t* a, const int* invalid, hipStream_t stream) {
     REQUIRE(a, "composite_layers: null args");
     REQUIRE(a->L >= 1 && a->L <= ENERF_MAX_FG_LAYERS && a->Ns >= 1 && a->L * a->Ns <= 16,
             "composite_layers: L=%d foreground layers x %d samples unsupported (L in 1..%d, L*n_samples <= 16)", a->L, a->Ns,
@@ -482,14 +487,26 @@ int enerf_composite_layers(const enerf_composite_layers_t* a, enerf_stream_t str
         REQUIRE((uintptr_t)a->fg_raw[l] % 16 == 0, "composite_layers: layer %d: fg_raw must be 16-byte aligned", l);
         if (int rc = check_window("composite_layers", a->H, a->W, a->win[l][0], a->win[l][1], a->win[l][2], a->win[l][3])) return rc;
     }
-    launch_composite_layers(*a, (hipStream_t)stream);
+    launch_composite_layers(*a, stream, invalid);
     return check_launch("composite_layers");
 }
+}  // namespace enerf
+extern "C" {
 int enerf_composite_prep(const enerf_composite_prep_t* a, enerf_stream_t stream) {
     CompositePrep job;
     if (int rc = composite_prep_job(a, &job)) return rc;
     launch_composite_prep(job, (hipStream_t)stream);
     return check_launch("composite_prep");
+}
+int enerf_composite_prep_indexed(const enerf_composite_prep_t* a, const int* view_idx, int V, float* cam_exts, float* cam_ixts,
+                                 enerf_stream_t stream) {
+    CompositePrep job;
+    if (int rc = composite_prep_job(a, &job)) return rc;
+    REQUIRE(view_idx && cam_exts && cam_ixts, "composite_prep_indexed: view_idx / cam_exts / cam_ixts is null");
+    REQUIRE(V >= 1, "composite_prep_indexed: V=%d views in the camera tables", V);
+    job.view_idx = view_idx; job.V = V; job.cam_exts = cam_exts; job.cam_ixts = cam_ixts;
+    launch_composite_prep(job, (hipStream_t)stream);
+    return check_launch("composite_prep_indexed");
 }
 
 }  // extern "C"

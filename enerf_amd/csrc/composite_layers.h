@@ -63,12 +63,25 @@ using CompositeLayers = enerf_composite_layers_t;
 // L * Ns register slots (padded with +inf, which stay last).  It exchanges NEIGHBOURS and only when the left one is strictly
 // greater, so samples of equal depth keep their concatenation order (layer, then sample): the order is deterministic, where
 // torch.sort promises none.  The background's Ns samples follow unsorted (utils.py:917-918).
+// `invalid` (nullptr: none) is a device flag of the cached frame: nonzero = a source-view index was outside the cache, and every
+// output of the level is NaN (the ReLUs upstream return 0 for NaN, so the views' NaN alone would reach the colours only).
 template <int NFP>
-__global__ __launch_bounds__(256) void k_composite_layers(CompositeLayers a) {
+__global__ __launch_bounds__(256) void k_composite_layers(CompositeLayers a, const int* __restrict__ invalid) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.H * a.W) return;
     const int y = p / a.W, x = p - y * a.W;
     const int Ns = a.Ns, nf = a.L * Ns, T = nf + Ns;
+    if (invalid != nullptr && invalid[0] != 0) {        // uniform
+        const float qnan = __int_as_float(0x7fc00000);
+        for (int i = 0; i < nf; ++i) a.z_vals[(long long)p * nf + i] = qnan;
+        for (int t = 0; t < T; ++t) {
+            *reinterpret_cast<float4*>(a.net_output + ((long long)p * T + t) * 4) = make_float4(qnan, qnan, qnan, qnan);
+            a.weights[(long long)p * T + t] = qnan;
+        }
+        a.rgb[(long long)p * 3 + 0] = qnan; a.rgb[(long long)p * 3 + 1] = qnan; a.rgb[(long long)p * 3 + 2] = qnan;
+        a.depth[p] = qnan;
+        return;
+    }
     int base[ENERF_MAX_FG_LAYERS];                      // the pixel's row in layer l's buffers, or -1
 #pragma unroll
     for (int l = 0; l < ENERF_MAX_FG_LAYERS; ++l) {
@@ -128,13 +141,13 @@ __global__ __launch_bounds__(256) void k_composite_layers(CompositeLayers a) {
     a.rgb[(long long)p * 3 + 0] = rgb0; a.rgb[(long long)p * 3 + 1] = rgb1; a.rgb[(long long)p * 3 + 2] = rgb2;
     a.depth[p] = dep;
 }
-void launch_composite_layers(const CompositeLayers& a, hipStream_t st) {
+void launch_composite_layers(const CompositeLayers& a, hipStream_t st, const int* invalid) {
     const int nf = a.L * a.Ns;
     const unsigned grid = (unsigned)cdiv(a.H * a.W, 256);
-    if (nf <= 2) ENERF_LAUNCH_SIMPLE(k_composite_layers<2>, grid, 256, 0, st, a);
-    else if (nf <= 4) ENERF_LAUNCH_SIMPLE(k_composite_layers<4>, grid, 256, 0, st, a);
-    else if (nf <= 8) ENERF_LAUNCH_SIMPLE(k_composite_layers<8>, grid, 256, 0, st, a);
-    else ENERF_LAUNCH_SIMPLE(k_composite_layers<16>, grid, 256, 0, st, a);      // L * Ns <= 16 (the C-ABI layer checks)
+    if (nf <= 2) ENERF_LAUNCH_SIMPLE(k_composite_layers<2>, grid, 256, 0, st, a, invalid);
+    else if (nf <= 4) ENERF_LAUNCH_SIMPLE(k_composite_layers<4>, grid, 256, 0, st, a, invalid);
+    else if (nf <= 8) ENERF_LAUNCH_SIMPLE(k_composite_layers<8>, grid, 256, 0, st, a, invalid);
+    else ENERF_LAUNCH_SIMPLE(k_composite_layers<16>, grid, 256, 0, st, a, invalid);      // L * Ns <= 16 (the C-ABI layer checks)
 }
 
 }  // namespace enerf

@@ -753,6 +753,13 @@ int run_frame(const enerf_frame_args_t* a, const enerf_source_cache_t* cache, co
 //   layer l (its lane stream): C[i][l].{dv, nf (i > 0), vol, feat3d, prob, depth, std, raw, z} of every level i, costreg_ws[l];
 //   background (caller's stream): f_bg[0..2], featws_bg, tex_bg, C[i][L].*, costreg_ws[L].
 // A layer's raw / z and the caller's outputs meet only in enerf_composite_layers, behind the join.
+//
+// A cached frame (enerf_forward_composite_cached; `cached` below) takes both nets' maps, the texels and the source cameras from an
+// enerf_composite_cache_t behind a device-side view index: the preparation launch reads its cameras through the index and leaves the
+// gathered rows in cam_exts / cam_ixts and the "an index was outside the cache" flag the merges read in `invalid` (shared: written
+// before the fork, read-only after), and the sources are two k_gather_sources
+// launches into the regions the FeatureNets and texel packs wrote — the foreground's on `side`, the background's on the caller's
+// stream, same owners as above.  No FeatureNet scratch, and no region for a feature map that no cost volume reads.
 // =====================================================================================================================
 constexpr int kCompCascades = ENERF_MAX_FG_LAYERS + 1;
 struct CompLevel {
@@ -769,6 +776,7 @@ struct CompCascadeLevel {
 };
 struct CompositePlan {
     size_t f_fg[3], f_bg[3], featws_fg, featws_bg, featws_bytes;
+    size_t cam_exts, cam_ixts, invalid;    // cached frame: the gathered (1,S,4,4) / (1,S,3,3) camera rows; "an index was outside the cache"
     CompLevel L[ENERF_MAX_LEVELS];
     CompCascadeLevel C[ENERF_MAX_LEVELS][kCompCascades];
     size_t costreg_ws[kCompCascades], costreg_ws_bytes[kCompCascades];
@@ -786,7 +794,7 @@ int check_comp_window(const char* grid, int level, int l, const int* wn, int h, 
     return ENERF_OK;
 }
 
-int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P) {
+int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P, bool cached = false) {
     REQUIRE(a, "forward_composite: null args");
     const enerf_cascade_t& c = a->cas;
     const int L = a->L;
@@ -794,10 +802,14 @@ int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P)
     REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "forward_composite: cas.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
     REQUIRE(a->S >= 2 && a->S <= 4 && a->H > 0 && a->W > 0 && a->H % 4 == 0 && a->W % 4 == 0,
             "forward_composite: bad frame shape S=%d H=%d W=%d (S in 2..4, H and W divisible by 4)", a->S, a->H, a->W);
-    REQUIRE(a->src_inps && a->bg_src_inps, "forward_composite: src_inps / bg_src_inps is null");
-    REQUIRE(a->src_exts && a->src_ixts && a->tar_ext && a->tar_ixt, "forward_composite: src_exts / src_ixts / tar_ext / tar_ixt is null");
+    if (!cached) {                         // (a cached frame takes these from the cache)
+        REQUIRE(a->src_inps && a->bg_src_inps, "forward_composite: src_inps / bg_src_inps is null");
+        REQUIRE(a->src_exts && a->src_ixts && a->tar_ext && a->tar_ixt, "forward_composite: src_exts / src_ixts / tar_ext / tar_ixt is null");
+    } else
+        REQUIRE(a->tar_ext && a->tar_ixt, "forward_composite: tar_ext / tar_ixt is null");
     REQUIRE(a->near_far, "forward_composite: near_far is null");
-    REQUIRE(a->feature_net_packed && a->feature_net_bg_packed, "forward_composite: feature_net_packed / feature_net_bg_packed is null");
+    if (!cached)
+        REQUIRE(a->feature_net_packed && a->feature_net_bg_packed, "forward_composite: feature_net_packed / feature_net_bg_packed is null");
     int covered = 0;
     while (covered < ENERF_MAX_LEVELS && a->bg_volume_planes[covered] > 0) ++covered;
     REQUIRE(c.num <= covered, "forward_composite: cas.num=%d levels but bg_volume_planes covers %d", c.num, covered);
@@ -813,11 +825,23 @@ int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P)
     auto take = [&](size_t nfloats) { size_t r = off; off += (nfloats + 63) / 64 * 64; return r; };   // 256-B aligned
     const FeatDims fd(a->H, a->W);
     const int S = a->S;
-    for (int l = 0; l < 3; ++l) P->f_fg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
-    for (int l = 0; l < 3; ++l) P->f_bg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
-    P->featws_bytes = enerf_feature_net_workspace_bytes(S, a->H, a->W);
-    P->featws_fg = take(P->featws_bytes / sizeof(float));
-    P->featws_bg = take(P->featws_bytes / sizeof(float));
+    if (!cached) {
+        for (int l = 0; l < 3; ++l) P->f_fg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+        for (int l = 0; l < 3; ++l) P->f_bg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+        P->featws_bytes = enerf_feature_net_workspace_bytes(S, a->H, a->W);
+        P->featws_fg = take(P->featws_bytes / sizeof(float));
+        P->featws_bg = take(P->featws_bytes / sizeof(float));
+    } else {                               // only the maps a cost volume reads; the cameras' rows instead of the FeatureNets' scratch
+        int segs = c.num;
+        for (int i = 0; i < c.num; ++i) segs += c.render_if[i] != 0;
+        REQUIRE(segs <= kGatherSegs, "forward_composite: cas.num=%d levels with %d rendered need %d gather segments per net (at most %d)",
+                c.num, segs - c.num, segs, kGatherSegs);
+        for (int l = 0; l < c.num && l < 3; ++l) P->f_fg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+        for (int l = 0; l < c.num && l < 3; ++l) P->f_bg[l] = take((size_t)S * fd.pixels(l) * fd.c[l]);
+        P->cam_exts = take((size_t)S * 16);
+        P->cam_ixts = take((size_t)S * 9);
+        P->invalid = take(64);
+    }
     for (int i = 0; i < c.num; ++i) {
         CompLevel& V = P->L[i];
         V.h = scaled(a->H, c.volume_scale[i]);
@@ -905,8 +929,30 @@ int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P)
     return ENERF_OK;
 }
 
+// what the host can see of a composite cache against the frame / cascade it is used with
+int check_composite_cache(const char* what, const enerf_composite_cache_t* k, const enerf_cascade_t& c, int H, int W) {
+    REQUIRE(k, "%s: null cache", what);
+    REQUIRE(k->V >= 1, "%s: cache has V=%d views", what, k->V);
+    REQUIRE(k->H == H && k->W == W, "%s: cache was built for %dx%d images (H, W), the frame has %dx%d", what, k->H, k->W, H, W);
+    REQUIRE(k->exts && k->ixts, "%s: cache has no exts / ixts", what);
+    size_t bits = (size_t)k->exts | (size_t)k->ixts;
+    for (int i = 0; i < c.num && i < ENERF_MAX_LEVELS; ++i) {
+        REQUIRE(k->fg_feat[i] && k->bg_feat[i], "%s: cache has no %s[%d], the feature map of cascade level %d", what,
+                k->fg_feat[i] ? "bg_feat" : "fg_feat", i, i);
+        bits |= (size_t)k->fg_feat[i] | (size_t)k->bg_feat[i];
+        if (!c.render_if[i]) continue;
+        REQUIRE(k->fg_tex[i] && k->bg_tex[i], "%s: cache has no %s[%d], the texel image of rendered level %d", what,
+                k->fg_tex[i] ? "bg_tex" : "fg_tex", i, i);
+        bits |= (size_t)k->fg_tex[i] | (size_t)k->bg_tex[i];
+    }
+    REQUIRE((bits & 15) == 0, "%s: cache buffers must be 16-byte aligned", what);
+    return ENERF_OK;
+}
+
 struct CompositeRun {
     const enerf_composite_frame_args_t* a = nullptr;
+    const enerf_composite_cache_t* cache = nullptr;  // cached frame: the maps, texels and cameras come from here
+    const int* view_idx = nullptr;
     CompositePlan P;
     hipStream_t st = nullptr;            // the caller's stream
     float* ws = nullptr;
@@ -940,11 +986,18 @@ struct CompositeRun {
     float* depth_of(int i, int k) const { return a->depth_map[i][k] ? a->depth_map[i][k] : ws + P.C[i][k].depth; }
     float* std_of(int i, int k) const { return a->std_map[i][k] ? a->std_map[i][k] : ws + P.C[i][k].std; }
     const float* rays_of(int i) const { return a->rays[i] ? a->rays[i] : ws + P.L[i].rays; }
+    // the source cameras of the raw renders: the batch's, or (cached frame) the rows the preparation leaves in the workspace
+    const float* src_exts() const { return cache ? ws + P.cam_exts : a->src_exts; }
+    const float* src_ixts() const { return cache ? ws + P.cam_ixts : a->src_ixts; }
 
     // the plan, and everything the host can refuse before the first launch
-    int begin(const enerf_composite_frame_args_t* args, enerf_stream_t stream) {
-        a = args;
-        if (int rc = make_composite_plan(a, &P)) return rc;
+    int begin(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* k, const int* idx, enerf_stream_t stream) {
+        a = args; cache = k; view_idx = idx;
+        if (int rc = make_composite_plan(a, &P, cache != nullptr)) return rc;
+        if (cache != nullptr) {
+            if (int rc = check_composite_cache("forward_composite_cached", cache, a->cas, a->H, a->W)) return rc;
+            REQUIRE(view_idx, "forward_composite_cached: null view_idx (an (S) int32 device array)");
+        }
         REQUIRE(a->workspace, "forward_composite: workspace is null");
         REQUIRE((uintptr_t)a->workspace % 16 == 0, "forward_composite: workspace must be 16-byte aligned");
         if (a->workspace_bytes < P.total_floats * sizeof(float))
@@ -957,12 +1010,14 @@ struct CompositeRun {
     }
 
     // ---- everything that depends on the cameras, near_far and the boxes alone, on the caller's stream in front of the fork: the
-    // preparation launch (all proj, level 0's planes of every cascade, every window's ray list) and the generated rays
+    // preparation launch (all proj, level 0's planes of every cascade, every window's ray list) and the generated rays.  A cached
+    // frame's launch reads the source cameras from the cache's tables through view_idx and writes the gathered rows beside the rest
     int prep() {
         const enerf_cascade_t& c = cas();
         enerf_composite_prep_t p;
         memset(&p, 0, sizeof(p));
-        p.src_ixts = a->src_ixts; p.src_exts = a->src_exts; p.tar_ixt = a->tar_ixt; p.tar_ext = a->tar_ext; p.near_far = a->near_far;
+        p.src_ixts = cache ? cache->ixts : a->src_ixts; p.src_exts = cache ? cache->exts : a->src_exts;
+        p.tar_ixt = a->tar_ixt; p.tar_ext = a->tar_ext; p.near_far = a->near_far;
         p.L = L; p.S = a->S; p.num_levels = c.num;
         p.fg_planes = P.C[0][0].D; p.bg_planes = P.C[0][L].D; p.h = P.L[0].h; p.w = P.L[0].w; p.depth_inv = c.depth_inv[0];
         for (int k = 0; k <= L; ++k) { p.dv[k] = ws + P.C[0][k].dv; p.nf[k] = ws + P.C[0][k].nf; }
@@ -978,6 +1033,10 @@ struct CompositeRun {
         }
         CompositePrep job;
         if (int rc = composite_prep_job(&p, &job)) return rc;
+        if (cache != nullptr) {
+            job.view_idx = view_idx; job.V = cache->V; job.cam_exts = ws + P.cam_exts; job.cam_ixts = ws + P.cam_ixts;
+            job.invalid = (int*)(ws + P.invalid);
+        }
         launch_composite_prep(job, st);
         if (int rc = check_launch("forward_composite: prep")) return rc;
         for (int i = 0; i < c.num; ++i) {
@@ -1019,11 +1078,31 @@ struct CompositeRun {
         }
         return ENERF_OK;
     }
+    // cached frame: one net's sources = one gather launch of the selected views' maps (the levels a cost volume reads) and texel images
+    // (the cameras came with the preparation)
+    int gather_of(float* const* feat, float* const* tex, const size_t* f, bool fg, LaneStream s) {
+        const FeatDims fd(a->H, a->W);
+        GatherJob J;
+        memset(&J, 0, sizeof(J));
+        J.V = cache->V; J.view_idx = view_idx;
+        auto add = [&J](const float* src, float* dst, long long floats_per_view) {
+            J.seg[J.nseg++] = GatherSeg{reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), floats_per_view / 4};
+        };
+        for (int i = 0; i < cas().num; ++i) add(feat[i], ws + f[i], fd.pixels(i) * fd.c[i]);
+        for (int i = 0; i < cas().num; ++i) {
+            const CompLevel& V = P.L[i];
+            if (V.render) add(tex[i], ws + (fg ? V.tex_fg : V.tex_bg), (long long)V.Hr * V.Wr * tex_stride(V.F));
+        }
+        launch_gather_sources(J, a->S, on(s));
+        return check_launch("forward_composite_cached: gather");
+    }
     int sources() {
-        int rc = sources_of(a->feature_net_packed, a->src_inps, P.f_fg, P.featws_fg, true, lane_of_sources());
+        int rc = cache ? gather_of(cache->fg_feat, cache->fg_tex, P.f_fg, true, lane_of_sources())
+                       : sources_of(a->feature_net_packed, a->src_inps, P.f_fg, P.featws_fg, true, lane_of_sources());
         if (forked && L >= 2) { lane->record(kEvFeats, kLaneSide); lane->wait(kLaneRender, kEvFeats); }
         if (rc != ENERF_OK) return rc;
-        return sources_of(a->feature_net_bg_packed, a->bg_src_inps, P.f_bg, P.featws_bg, false, kLaneMain);
+        return cache ? gather_of(cache->bg_feat, cache->bg_tex, P.f_bg, false, kLaneMain)
+                     : sources_of(a->feature_net_bg_packed, a->bg_src_inps, P.f_bg, P.featws_bg, false, kLaneMain);
     }
 
     // ---- cascade k, level i, up to its depth / std maps (network_composite.py:83-113): depth planes (level 0's came with the
@@ -1062,7 +1141,7 @@ struct CompositeRun {
         memset(&r, 0, sizeof(r));
         r.rays8 = rays_of(i); r.depth_map = pdepth[k]; r.std_map = pstd[k]; r.nf_map = pnf[k]; r.map_h = V.h; r.map_w = V.w;
         r.tex = ws + (fg ? V.tex_fg : V.tex_bg); r.vol = nullptr;
-        r.src_exts = a->src_exts; r.src_ixts = a->src_ixts; r.tar_ext = a->tar_ext; r.packed = a->nerf_packed[i][k];
+        r.src_exts = src_exts(); r.src_ixts = src_ixts(); r.tar_ext = a->tar_ext; r.packed = a->nerf_packed[i][k];
         r.raw = ws + K.raw; r.z = ws + K.z;
         r.B = 1; r.N = V.Hr * V.Wr; r.S = a->S; r.n_samples = V.Ns; r.depth_inv = V.inv; r.Hr = V.Hr; r.Wr = V.Wr; r.F = V.F;
         r.render_scale = (float)cas().render_scale[i];
@@ -1083,13 +1162,13 @@ struct CompositeRun {
         m.bg_raw = ws + P.C[i][L].raw; m.bg_z = ws + P.C[i][L].z;
         m.L = L; m.Ns = V.Ns; m.H = V.Hr; m.W = V.Wr; m.white_bkgd = 0;
         m.rgb = a->rgb[i]; m.depth = a->depth[i]; m.weights = a->weights[i]; m.net_output = a->net_output[i]; m.z_vals = a->z_vals[i];
-        return enerf_composite_layers(&m, st);
+        return composite_layers_run(&m, cache ? (const int*)(ws + P.invalid) : nullptr, st);      // (uncached: enerf_composite_layers itself)
     }
 };
 
-int run_composite(const enerf_composite_frame_args_t* a, enerf_stream_t stream) {
+int run_composite(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
     CompositeRun R;
-    int rc = R.begin(a, stream);
+    int rc = R.begin(a, cache, view_idx, stream);
     if (rc != ENERF_OK) return rc;
     rc = R.prep();
     if (rc != ENERF_OK) return rc;                 // (nothing forked yet)
@@ -1216,6 +1295,96 @@ size_t enerf_forward_composite_workspace_bytes(const enerf_composite_frame_args_
     return P.total_floats * sizeof(float);
 }
 
-int enerf_forward_composite(const enerf_composite_frame_args_t* a, enerf_stream_t stream) { return run_composite(a, stream); }
+int enerf_forward_composite(const enerf_composite_frame_args_t* a, enerf_stream_t stream) { return run_composite(a, nullptr, nullptr, stream); }
+
+size_t enerf_forward_composite_cached_workspace_bytes(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache) {
+    CompositePlan P;
+    if (make_composite_plan(a, &P, true) != ENERF_OK) return 0;
+    if (check_composite_cache("forward_composite_cached", cache, a->cas, a->H, a->W) != ENERF_OK) return 0;
+    return P.total_floats * sizeof(float);
+}
+
+int enerf_forward_composite_cached(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache, const int* view_idx,
+                                   enerf_stream_t stream) {
+    REQUIRE(cache, "forward_composite_cached: null cache");
+    return run_composite(a, cache, view_idx, stream);
+}
+
+// ---- the composite cache itself: sizes for a cascade, and the build (per net the frame's FeatureNet and texel-pack calls over the V
+// views, <= 4 at a time; a map the cache does not keep lives in the workspace for the length of its chunk) ----
+int enerf_composite_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, long long* floats) {
+    REQUIRE(cas && floats, "composite_cache_sizes: null pointer");
+    const enerf_cascade_t& c = *cas;
+    REQUIRE(c.num >= 1 && c.num <= ENERF_MAX_LEVELS, "composite_cache_sizes: cas.num=%d unsupported (1..%d)", c.num, ENERF_MAX_LEVELS);
+    REQUIRE(V >= 1 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "composite_cache_sizes: bad shape V=%d H=%d W=%d (H and W divisible by 4)", V, H, W);
+    const FeatDims fd(H, W);
+    for (int i = 0; i < ENERF_COMPOSITE_CACHE_BUFFERS; ++i) floats[i] = 0;
+    for (int i = 0; i < c.num; ++i) {
+        floats[i] = floats[6 + i] = (long long)V * fd.pixels(i) * fd.c[i];
+        if (!c.render_if[i]) continue;
+        const int Hr = scaled(H, c.render_scale[i]), Wr = scaled(W, c.render_scale[i]);
+        if (int rc = check_render_feat("composite_cache_sizes", c, i, fd, Hr, Wr, true)) return rc;
+        floats[3 + i] = floats[9 + i] = (long long)V * Hr * Wr * tex_stride(c.nerf_model_feat_ch[i] + 3);
+    }
+    floats[12] = (long long)V * 16;
+    floats[13] = (long long)V * 9;
+    return ENERF_OK;
+}
+
+// the FeatureNet workspace of 4 images, then the three maps of 4 images (a net writes all three; the cache keeps some)
+static size_t composite_cache_scratch_map(int H, int W, int l) {
+    const FeatDims fd(H, W);
+    size_t off = enerf_feature_net_workspace_bytes(4, H, W) / sizeof(float);
+    for (int k = 0; k < l; ++k) off += (size_t)4 * fd.pixels(k) * fd.c[k];
+    return off;
+}
+size_t enerf_composite_cache_build_workspace_bytes(int H, int W) { return composite_cache_scratch_map(H, W, 3) * sizeof(float); }
+
+int enerf_composite_cache_build(const enerf_composite_cache_t* cache, const float* src_inps, const float* bg_src_inps, const float* exts,
+                                const float* ixts, const float* feature_net_packed, const float* feature_net_bg_packed,
+                                const enerf_cascade_t* cas, int chunk, void* workspace, size_t workspace_bytes,
+                                const enerf_options_t* options, enerf_stream_t stream) {
+    REQUIRE(cache && cas, "composite_cache_build: null cache / cascade");
+    REQUIRE(src_inps && bg_src_inps && exts && ixts && feature_net_packed && feature_net_bg_packed && workspace,
+            "composite_cache_build: null pointer");
+    if (chunk == 0) chunk = 4;
+    REQUIRE(chunk >= 1 && chunk <= 4, "composite_cache_build: chunk=%d (1..4 images per FeatureNet call)", chunk);
+    const int V = cache->V, H = cache->H, W = cache->W;
+    long long floats[ENERF_COMPOSITE_CACHE_BUFFERS];
+    if (int rc = enerf_composite_cache_sizes(cas, V, H, W, floats)) return rc;
+    if (int rc = check_composite_cache("composite_cache_build", cache, *cas, H, W)) return rc;
+    REQUIRE((uintptr_t)workspace % 16 == 0, "composite_cache_build: workspace must be 16-byte aligned");
+    if (workspace_bytes < enerf_composite_cache_build_workspace_bytes(H, W))
+        return fail(ENERF_EWORKSPACE, "composite_cache_build: workspace too small");
+    const FeatDims fd(H, W);
+    const size_t featws_bytes = enerf_feature_net_workspace_bytes(4, H, W);
+    for (int v0 = 0; v0 < V; v0 += chunk) {
+        const int n = V - v0 < chunk ? V - v0 : chunk;
+        const float* img = src_inps + (size_t)v0 * 3 * H * W;          // BOTH nets read src_inps; bg_src_inps only colours
+        for (int net = 0; net < 2; ++net) {
+            float* const* feat = net == 0 ? cache->fg_feat : cache->bg_feat;
+            float* const* tex = net == 0 ? cache->fg_tex : cache->bg_tex;
+            const float* rgb = (net == 0 ? src_inps : bg_src_inps) + (size_t)v0 * 3 * H * W;
+            float* m[3];
+            for (int l = 0; l < 3; ++l)
+                m[l] = l < cas->num ? feat[l] + (size_t)v0 * fd.pixels(l) * fd.c[l] : (float*)workspace + composite_cache_scratch_map(H, W, l);
+            if (int rc = feature_net_stage_job(net == 0 ? feature_net_packed : feature_net_bg_packed, img, n, H, W, m[0], m[1], m[2], 8, workspace,
+                                               featws_bytes, ENERF_FEAT_ALL, options, (hipStream_t)stream, nullptr, nullptr))
+                return rc;
+            for (int i = 0; i < cas->num; ++i) {
+                if (!cas->render_if[i]) continue;
+                const int fl = cas->render_im_feat_level[i], TEX = tex_stride(fd.c[fl] + 3);
+                if (int rc = enerf_pack_texels_cl(m[fl], fd.c[fl], rgb, H, W, fd.h[fl], fd.w[fl], TEX, n,
+                                                  tex[i] + (size_t)v0 * fd.pixels(fl) * TEX, stream))
+                    return rc;
+            }
+        }
+    }
+    GatherJob J;                                        // the cameras: slot v takes view v
+    memset(&J, 0, sizeof(J));
+    J.V = V; J.exts = exts; J.ixts = ixts; J.dst_exts = cache->exts; J.dst_ixts = cache->ixts;
+    launch_gather_sources(J, V, (hipStream_t)stream);
+    return check_launch("composite_cache_build");
+}
 
 }  // extern "C"

@@ -288,7 +288,9 @@ void launch_feature_volume_window(const float* feat_nhwc, const float* proj, con
 void launch_depth_regression_window(const float* prob, const float* dv, int B, int D, int h, int w, int x0, int y0, int ww, int wh,
                                     int depth_inv, float* depth, float* std, hipStream_t st);
 void launch_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* index, int* count, hipStream_t st);
-void launch_composite_layers(const enerf_composite_layers_t& a, hipStream_t st);
+void launch_composite_layers(const enerf_composite_layers_t& a, hipStream_t st, const int* invalid = nullptr);
+// enerf_composite_layers with the cached frame's device flag (nonzero: every output NaN; nullptr: the C entry itself)
+int composite_layers_run(const enerf_composite_layers_t* a, const int* invalid, hipStream_t st);
 // the composite frame's camera-only preparation (prep_job.h CompositePrep, geometry.hip k_composite_prep): composite_prep_job checks
 // the C arguments and lays the job out (ENERF_EINVAL + message, nothing launched), launch_composite_prep runs it
 struct CompositePrep;

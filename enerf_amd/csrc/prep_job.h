@@ -111,13 +111,53 @@ struct CompositePrep {
     struct Window { int x0, y0, ww, wh, Wr, block0, blocks; int *index, *count; } win[kCompositePrepWindows];
     int n_win;
     int nblocks;
+    // A cached frame (enerf_forward_composite_cached, enerf_composite_prep_indexed): the source cameras sit in a cache's tables behind a
+    // device-side index.  pj[*].src_exts / src_ixts are then the (V,4,4) / (V,3,3) tables, source camera s is their row view_idx[s],
+    // and block 0 also leaves the S gathered rows in cam_exts (S,4,4) / cam_ixts (S,3,3) for the raw renders.  An index outside [0,V)
+    // is never used as an address: that camera's rows and matrices are NaN, and *invalid (optional) is 1 instead of 0: the frame's
+    // merges then write NaN (k_composite_layers).  view_idx == nullptr: rows 0 .. S-1 as they are, as ever.
+    const int* view_idx;
+    int V;
+    float *cam_exts, *cam_ixts;
+    int* invalid;
 };
 inline int composite_prep_job_blocks(long long elements, int threads) {
     const long long nb = (elements + threads - 1) / threads;
     return (int)(nb < 1 ? 1 : nb > kCompositePrepJobBlocks ? kCompositePrepJobBlocks : nb);
 }
+// block 0 of an indexed job: the projection matrices from the indexed rows, and the rows themselves
+__device__ __forceinline__ void composite_prep_indexed_cameras(const CompositePrep& J, int tid, int threads) {
+    const float qnan = __int_as_float(0x7fc00000);
+#pragma unroll 1
+    for (int l = 0; l < 3; ++l) {
+        const ProjJob& pj = J.pj[l];
+        if (pj.proj == nullptr) continue;
+        for (int q = tid; q < pj.S; q += threads) {
+            const int v = J.view_idx[q];
+            if (v >= 0 && v < J.V)      // (row v as "camera 0" of a one-camera table: proj_one's arithmetic, so its bits)
+                proj_one(0, pj.src_ixts + (long long)v * 9, pj.src_exts + (long long)v * 16, pj.tar_ixt, pj.tar_ext, pj.S, pj.src_scale,
+                         pj.tar_scale, pj.proj + q * 12);
+            else
+                for (int k = 0; k < 12; ++k) pj.proj[q * 12 + k] = qnan;
+        }
+    }
+    const int S = J.pj[0].S;
+    if (tid == 0 && J.invalid != nullptr) {
+        int bad = 0;
+        for (int q = 0; q < S; ++q) bad |= (J.view_idx[q] < 0 || J.view_idx[q] >= J.V) ? 1 : 0;
+        J.invalid[0] = bad;
+    }
+    for (int i = tid; i < S * 25; i += threads) {
+        const int q = i / 25, t = i - q * 25;
+        const int v = J.view_idx[q];
+        const bool ok = v >= 0 && v < J.V;
+        if (t < 16) J.cam_exts[q * 16 + t] = ok ? J.pj[0].src_exts[(long long)v * 16 + t] : qnan;
+        else J.cam_ixts[q * 9 + (t - 16)] = ok ? J.pj[0].src_ixts[(long long)v * 9 + (t - 16)] : qnan;
+    }
+}
 __device__ __forceinline__ void composite_prep_block(const CompositePrep& J, int vb, int tid, int threads) {
-    if (vb == 0) {
+    if (vb == 0 && J.view_idx != nullptr) composite_prep_indexed_cameras(J, tid, threads);
+    else if (vb == 0) {
 #pragma unroll 1
         for (int l = 0; l < 3; ++l)
             if (J.pj[l].proj != nullptr)

@@ -170,6 +170,15 @@ class SourceCacheStruct(C.Structure):
 SOURCE_CACHE_BUFFERS = 5 + MAX_LEVELS
 
 
+class CompositeCacheStruct(C.Structure):
+    """``enerf_composite_cache_t``."""
+    _fields_ = ([(n, _fL) for n in ("fg_feat", "fg_tex", "bg_feat", "bg_tex")] + [("exts", _f), ("ixts", _f)]
+                + [(n, _i) for n in ("V", "H", "W")])
+
+
+COMPOSITE_CACHE_BUFFERS = 4 * MAX_LEVELS + 2
+
+
 class _ConvWB(C.Structure):
     _fields_ = [("w", _f), ("b", _f)]
 
@@ -339,6 +348,13 @@ _SIGNATURES = {
     "enerf_composite_prep": (_i, [C.POINTER(CompositePrepArgs), _f]),
     "enerf_forward_composite_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs)]),
     "enerf_forward_composite": (_i, [C.POINTER(CompositeFrameArgs), _f]),
+    "enerf_composite_cache_sizes": (_i, [C.POINTER(Cascade), _i, _i, _i, C.POINTER(_ll)]),
+    "enerf_composite_cache_build_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "enerf_composite_cache_build": (_i, [C.POINTER(CompositeCacheStruct), _f, _f, _f, _f, _f, _f, C.POINTER(Cascade), _i, C.c_void_p,
+                                         C.c_size_t, C.POINTER(Options), _f]),
+    "enerf_composite_prep_indexed": (_i, [C.POINTER(CompositePrepArgs), C.c_void_p, _i, _f, _f, _f]),
+    "enerf_forward_composite_cached_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct)]),
+    "enerf_forward_composite_cached": (_i, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct), C.c_void_p, _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -753,13 +769,16 @@ class EnerfLib:
         return res
 
     def composite_prep(self, src_ixts, src_exts, tar_ixt, tar_ext, near_far, scales, fg_planes, bg_planes, h, w, depth_inv, rasters,
-                       windows):
+                       windows, view_idx=None):
         """The composite frame's camera-only preparation in one launch.  ``near_far`` (L+1, 2), the background's row last;
         ``scales`` = [(src_scale, tar_scale)] per level; ``rasters`` = [(Hr, Wr) or None] per level; ``windows[i]`` = the L windows
         (x0, y0, ww, wh) of level i's raster (ignored where the raster is None).  Returns ``(proj, dv, nf, index)``: proj[i]
-        (1,S,3,4) per level; dv[c] (1,D_c,h,w), nf[c] (1,2,h,w) per cascade; index[i] = [(index, count)] per window, or None."""
+        (1,S,3,4) per level; dv[c] (1,D_c,h,w), nf[c] (1,2,h,w) per cascade; index[i] = [(index, count)] per window, or None.
+        With ``view_idx`` (S) int32 on the device (``enerf_composite_prep_indexed``) ``src_ixts`` / ``src_exts`` are the (V,3,3) /
+        (V,4,4) tables of a cache, source camera s is their row ``view_idx[s]``, and the gathered rows are returned too:
+        ``(proj, dv, nf, index, (cam_exts (1,S,4,4), cam_ixts (1,S,3,3)))``."""
         dev = src_ixts.device
-        S = int(src_ixts.shape[1])
+        S = int(src_ixts.shape[1]) if view_idx is None else int(view_idx.numel())
         L = int(near_far.shape[0]) - 1
         if not 1 <= L <= MAX_FG_LAYERS or len(scales) > MAX_LEVELS:
             raise EnerfError(f"composite_prep: L={L} layers (1..{MAX_FG_LAYERS}), {len(scales)} levels (at most {MAX_LEVELS})")
@@ -787,6 +806,13 @@ class EnerfLib:
             dv.append(torch.empty((1, max(D, 0), max(int(h), 0), max(int(w), 0)), dtype=torch.float32, device=dev))
             nf.append(torch.empty((1, 2, max(int(h), 0), max(int(w), 0)), dtype=torch.float32, device=dev))
             a.dv[c], a.nf[c] = dv[-1].data_ptr(), nf[-1].data_ptr()
+        if view_idx is not None:
+            if view_idx.dtype != torch.int32 or not view_idx.is_contiguous() or view_idx.device != dev:
+                raise EnerfError("composite_prep: view_idx must be a contiguous int32 tensor on the cameras' device")
+            cams = (torch.empty((1, S, 4, 4), dtype=torch.float32, device=dev), torch.empty((1, S, 3, 3), dtype=torch.float32, device=dev))
+            self._check(self.dll.enerf_composite_prep_indexed(C.byref(a), view_idx.data_ptr(), int(src_exts.shape[0]), _ptr(cams[0]),
+                                                              _ptr(cams[1]), self.stream_of(src_ixts)), "composite_prep_indexed")
+            return proj, dv, nf, index, cams
         self._check(self.dll.enerf_composite_prep(C.byref(a), self.stream_of(src_ixts)), "composite_prep")
         return proj, dv, nf, index
 
@@ -798,6 +824,35 @@ class EnerfLib:
 
     def forward_composite(self, args: "CompositeFrameArgs", stream):
         self._check(self.dll.enerf_forward_composite(C.byref(args), stream), "forward_composite")
+
+    # -- the composite network's source-view cache (enerf_amd/composite_cache.py owns the tensors) --------
+    def composite_cache_sizes(self, cas: "Cascade", V: int, H: int, W: int):
+        """Floats per buffer of an ``enerf_composite_cache_t`` (0 = not needed): fg_feat[0..2], fg_tex[0..2], bg_feat[0..2],
+        bg_tex[0..2], exts, ixts."""
+        floats = (_ll * COMPOSITE_CACHE_BUFFERS)()
+        self._check(self.dll.enerf_composite_cache_sizes(C.byref(cas), V, H, W, floats), "composite_cache_sizes")
+        return list(floats)
+
+    def composite_cache_build_workspace(self, H: int, W: int, device):
+        """Scratch of ``enerf_composite_cache_build`` for HxW images (it does not depend on V)."""
+        nb = self.dll.enerf_composite_cache_build_workspace_bytes(H, W)
+        return torch.empty(((nb + 3) // 4,), dtype=torch.float32, device=device)
+
+    def composite_cache_build(self, cache: "CompositeCacheStruct", src_inps, bg_src_inps, exts, ixts, packed, packed_bg, cas: "Cascade",
+                              chunk=0, options=None, workspace=None):
+        ws = workspace if workspace is not None else self.composite_cache_build_workspace(cache.H, cache.W, src_inps.device)
+        self._check(self.dll.enerf_composite_cache_build(C.byref(cache), _ptr(src_inps), _ptr(bg_src_inps), _ptr(exts), _ptr(ixts),
+                                                         _ptr(packed), _ptr(packed_bg), C.byref(cas), int(chunk), ws.data_ptr(),
+                                                         ws.numel() * 4, _opt(options), self.stream_of(src_inps)), "composite_cache_build")
+
+    def forward_composite_cached_workspace_bytes(self, args: "CompositeFrameArgs", cache: "CompositeCacheStruct") -> int:
+        n = self.dll.enerf_forward_composite_cached_workspace_bytes(C.byref(args), C.byref(cache))
+        if n == 0:
+            raise EnerfError(f"forward_composite_cached: {self.dll.enerf_last_error().decode()}")
+        return n
+
+    def forward_composite_cached(self, args: "CompositeFrameArgs", cache: "CompositeCacheStruct", view_idx_ptr, stream):
+        self._check(self.dll.enerf_forward_composite_cached(C.byref(args), C.byref(cache), view_idx_ptr, stream), "forward_composite_cached")
 
     # -- backward kernels (training path; wrapped by enerf_amd/autograd.py) -----------------------------
     def build_feature_volume_bwd(self, feat_cl, proj, dv, grad_vol):

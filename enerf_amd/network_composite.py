@@ -17,9 +17,15 @@ forked onto the library's side lane (``options.single_stream`` keeps the frame o
 driver="staged")`` keeps the earlier path — one ctypes call per stage, the same kernels, the same bits — and a ``stage_hook`` selects
 it for that frame too (per-stage timing, tools/time_composite.py).
 
+A viewer that draws many target cameras from one rig of V source views per time frame runs the two FeatureNets once per time frame:
+``cache = net.cache_sources(inps, bg_inps, exts, ixts)`` (enerf_amd/composite_cache.py), then ``net.forward_cached(cache, view_idx,
+batch)`` per camera — ``enerf_forward_composite_cached``, the same frame with both nets' maps, the texels and the source cameras
+gathered by a device-resident view index, bit for bit ``forward`` on those views.
+
 Restrictions, all stated in DESIGN.md §8: inference only (``forward`` raises in training mode); ``B == 1`` (the reference reads
-``batch['bbox'][0]`` for every batch element); ``feature_backend="hip"``; no source cache, ``SequencePlayer`` or multi-GPU
-driver; at most four foreground layers with ``num_fg_layers * num_samples <= 16`` per level.
+``batch['bbox'][0]`` for every batch element); ``feature_backend="hip"``; no ``SequencePlayer`` or multi-GPU driver; the cached
+frame has no staged form (``forward_cached`` with a ``stage_hook`` raises); at most four foreground layers with
+``num_fg_layers * num_samples <= 16`` per level.
 
 The output dict has the reference's keys per rendered level — ``rgb``, ``depth``, ``weights``, ``net_output``, ``z_vals``, each
 suffixed ``_level{i}`` — except ``idx``: that is ``torch.sort``'s permutation, which is unspecified among samples of equal depth
@@ -122,6 +128,7 @@ class Network(nn.Module):
             setattr(self, f"cost_reg_{i}_bg", CostRegParams(int(32 * (2 ** (-i))), full=False))
             setattr(self, f"nerf_{i}_bg", NerfCompositeParams(cas.nerf_model_feat_ch[i] + 3, self.cfg.viewdir_agg))
         self._packed: Dict[str, torch.Tensor] = {}
+        self._packed_gen = 0                           # moves on whenever the packed images are dropped: a source cache built before is stale
         self._shapes: "OrderedDict[tuple, dict]" = OrderedDict()     # frame shape -> its buffers (_shape_buffers)
         self.intermediates: Dict[str, torch.Tensor] = {}
         self.stage_hook = None                         # optional callable(stage name), called between the stages of forward()
@@ -135,6 +142,7 @@ class Network(nn.Module):
 
     def invalidate_packed(self):
         self._packed = {}
+        self._packed_gen = getattr(self, "_packed_gen", 0) + 1
         self._shapes = OrderedDict()
 
     def _apply(self, fn, *a, **k):
@@ -184,7 +192,7 @@ class Network(nn.Module):
         return [tuple(b) for b in bbox[:self.num_fg_layers]]
 
     def _shape_buffers(self, key):
-        """The buffers of one frame shape — (H, W, S, boxes, device) — allocated on the first frame of that shape and reused by every
+        """The buffers of one frame shape — (H, W, S, boxes, which levels bring their own rays, device) — allocated on the first frame of that shape and reused by every
         later one; the few most recent shapes are kept (moving boxes change the windowed buffers' sizes)."""
         st = self._shapes.get(key)
         if st is None:
@@ -202,6 +210,18 @@ class Network(nn.Module):
                 t = st[name] = torch.empty(tuple(int(v) for v in shape), dtype=dtype, device=dev)
             return t
         return st, buf
+
+    @staticmethod
+    def _holder(buf, dev):
+        def held(name, t, shape):
+            """``t`` if the kernels can read it in place, else its copy in the shape's buffer (no allocation either way)."""
+            t = t.reshape(shape)
+            if t.dtype == torch.float32 and t.is_contiguous() and t.device == dev:
+                return t
+            b_ = buf(name, shape)
+            b_.copy_(t)
+            return b_
+        return held
 
     def _texels(self, lib, buf, name, feats, src, level, H, W):
         cas = self.cfg.cas
@@ -229,17 +249,11 @@ class Network(nn.Module):
         near_far = batch["near_far"]
         if tuple(near_far.shape) != (1, L + 1, 2):
             raise ValueError(f"network_composite: near_far must be (1, {L + 1}, 2): one range per foreground layer, the background's last")
-        st, buf = self._shape_buffers((H, W, S, tuple(boxes), dev))
+        # (generated rays live in the frame's workspace: a batch with and one without rays_{i} are two shapes)
+        own_rays = tuple(batch.get(f"rays_{i}") is not None for i in range(cas.num))
+        st, buf = self._shape_buffers((H, W, S, tuple(boxes), own_rays, dev))
         hook = self.stage_hook if self.stage_hook is not None else (lambda name: None)
-
-        def held(name, t, shape):
-            """``t`` if the kernels can read it in place, else its copy in the shape's buffer (no allocation either way)."""
-            t = t.reshape(shape)
-            if t.dtype == torch.float32 and t.is_contiguous() and t.device == dev:
-                return t
-            b_ = buf(name, shape)
-            b_.copy_(t)
-            return b_
+        held = self._holder(buf, dev)
         exts, ixts = held("src_exts", batch["src_exts"], (1, S, 4, 4)), held("src_ixts", batch["src_ixts"], (1, S, 3, 3))
         tar_ext, tar_ixt = held("tar_ext", batch["tar_ext"], (1, 4, 4)), held("tar_ixt", batch["tar_ixt"], (1, 3, 3))
         src4 = held("src_inps", src, (S, 3, H, W))
@@ -331,10 +345,58 @@ class Network(nn.Module):
         self.intermediates = inter
         return ret
 
-    def _forward_call(self, batch, st, buf, held, boxes, inputs, S, H, W):
+    # -- source-view cache (enerf_amd/composite_cache.py) -------------------------------------------
+    def cache_sources(self, inps, bg_inps, exts, ixts, chunk: int = 0):
+        """What both FeatureNets make of the V views a time frame draws its source views from, the render texels (the
+        foreground's coloured by ``inps``, the background's by ``bg_inps``) and the cameras, computed once: ``inps`` / ``bg_inps``
+        (V,3,H,W) float32 in [-1,1] or (V,H,W,3) uint8, ``exts`` (V,4,4), ``ixts`` (V,3,3).  Eval mode only.
+        ``CompositeSourceCache.rebuild`` takes the next time frame in place."""
+        from .composite_cache import CompositeSourceCache
+        return CompositeSourceCache(self, inps, bg_inps, exts, ixts, chunk)
+
+    def forward_cached(self, cache, view_idx, batch):
+        """``forward`` with the source views named by ``view_idx`` — an int32 DEVICE tensor (S,) or (1,S), e.g. the output of
+        ``EnerfLib.select_views`` — taken from ``cache``; ``batch`` carries ``tar_ext``, ``tar_ixt``, ``near_far`` (1,L+1,2), ``bbox``
+        and optionally ``rays_{i}``.  The index is never read on the host; anything else that holds integer indices is converted
+        and uploaded first.  Same output dict, ``intermediates``, per-shape buffers and ``options`` as ``forward``, bit for bit its
+        frame on those views; always ONE C call (``enerf_forward_composite_cached``), whatever ``driver`` is."""
+        if self.training:
+            raise RuntimeError("network_composite: inference only — forward_cached() has no training path; call net.eval()")
+        if self.stage_hook is not None:
+            raise RuntimeError("network_composite: forward_cached is one C call and has no staged form: clear stage_hook "
+                               "(per-stage timing runs forward on hand-gathered views)")
+        if cache.packed_gen != self._packed_gen:
+            raise RuntimeError("forward_cached: the cache is empty or the network's weights changed (load_state_dict / .to()) after "
+                               "it was built; rebuild it (cache.rebuild(...)) or call cache_sources again")
+        if not torch.is_tensor(view_idx):
+            import numpy as np
+            view_idx = torch.from_numpy(np.ascontiguousarray(view_idx))
+        if view_idx.is_floating_point() or view_idx.dtype == torch.bool or view_idx.dim() not in (1, 2) or \
+                (view_idx.dim() == 2 and view_idx.shape[0] != 1):
+            raise ValueError("forward_cached: view_idx must hold integer view indices, (S,) or (1,S)")
+        if view_idx.dtype != torch.int32 or view_idx.device != cache.device or not view_idx.is_contiguous():
+            view_idx = view_idx.to(device=cache.device, dtype=torch.int32).contiguous()
+        dev, L = cache.device, self.num_fg_layers
+        if batch["tar_ext"].device != dev:
+            raise ValueError("forward_cached: cache and batch must live on one device")
+        S, H, W = int(view_idx.numel()), cache.H, cache.W
+        boxes = self._boxes(batch)
+        near_far = batch["near_far"]
+        if tuple(near_far.shape) != (1, L + 1, 2):
+            raise ValueError(f"network_composite: near_far must be (1, {L + 1}, 2): one range per foreground layer, the background's last")
+        own_rays = tuple(batch.get(f"rays_{i}") is not None for i in range(self.cfg.cas.num))
+        st, buf = self._shape_buffers(("cached", H, W, S, tuple(boxes), own_rays, dev))
+        held = self._holder(buf, dev)
+        tar_ext, tar_ixt = held("tar_ext", batch["tar_ext"], (1, 4, 4)), held("tar_ixt", batch["tar_ixt"], (1, 3, 3))
+        nfs = buf("near_far", (L + 1, 1, 2))
+        nfs.copy_(near_far.reshape(L + 1, 1, 2))
+        return self._forward_call(batch, st, buf, held, boxes, (None, None, None, None, tar_ext, tar_ixt, nfs), S, H, W, cache, view_idx)
+
+    def _forward_call(self, batch, st, buf, held, boxes, inputs, S, H, W, cache=None, view_idx=None):
         """The frame as ONE C call (enerf_forward_composite): the shape's outputs, depth / std maps and one workspace tensor are handed
         to the driver, which runs the stages of the staged path below ``forward`` itself — same kernels, same bits — with the
-        foreground layers forked onto the library's side lane unless ``options.single_stream``."""
+        foreground layers forked onto the library's side lane unless ``options.single_stream``.  With ``cache`` and ``view_idx`` it is
+        the cached frame (enerf_forward_composite_cached): no images, source cameras or FeatureNet weights in the argument block."""
         cas, lib, L = self.cfg.cas, self.lib, self.num_fg_layers
         whos = [f"layer{l}" for l in range(L)] + ["bg"]
         a = st.get("call.args")
@@ -343,8 +405,9 @@ class Network(nn.Module):
             for l, box in enumerate(boxes):
                 for k in range(4):
                     a.bbox[l][k] = float(box[k])
-            a.feature_net_packed = self._packed_weights("feature_net").data_ptr()
-            a.feature_net_bg_packed = self._packed_weights("feature_net_bg").data_ptr()
+            if cache is None:
+                a.feature_net_packed = self._packed_weights("feature_net").data_ptr()
+                a.feature_net_bg_packed = self._packed_weights("feature_net_bg").data_ptr()
             outs, inter = {}, {}
             for i in range(cas.num):
                 a.bg_volume_planes[i] = BG_PLANES[i]
@@ -367,7 +430,8 @@ class Network(nn.Module):
                     outs.update({f"{k}_level{i}": v.unsqueeze(0) for k, v in out.items()})
             st["call.outs"], st["call.inter"] = outs, inter
         src4, bg4, exts, ixts, tar_ext, tar_ixt, nfs = inputs
-        a.src_inps, a.bg_src_inps, a.src_exts, a.src_ixts = src4.data_ptr(), bg4.data_ptr(), exts.data_ptr(), ixts.data_ptr()
+        if cache is None:
+            a.src_inps, a.bg_src_inps, a.src_exts, a.src_ixts = src4.data_ptr(), bg4.data_ptr(), exts.data_ptr(), ixts.data_ptr()
         a.tar_ext, a.tar_ixt, a.near_far = tar_ext.data_ptr(), tar_ixt.data_ptr(), nfs.data_ptr()
         for i in range(cas.num):
             rays = batch.get(f"rays_{i}") if cas.render_if[i] else None
@@ -380,9 +444,13 @@ class Network(nn.Module):
         opts = self.options                              # (kept alive by self for the length of the call)
         a.options = None if opts is None else C.pointer(opts)
         if "call.args" not in st:                        # one workspace per shape, sized by the plan (which refuses a bad frame here)
-            ws = buf("call.ws", ((lib.forward_composite_workspace_bytes(a) + 3) // 4,))
+            nbytes = lib.forward_composite_workspace_bytes(a) if cache is None else lib.forward_composite_cached_workspace_bytes(a, cache.struct)
+            ws = buf("call.ws", ((nbytes + 3) // 4,))
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
             st["call.args"] = a
-        lib.forward_composite(a, lib.stream_of(src4))
+        if cache is None:
+            lib.forward_composite(a, lib.stream_of(src4))
+        else:
+            lib.forward_composite_cached(a, cache.struct, view_idx.data_ptr(), lib.stream_of(tar_ext))
         self.intermediates = dict(st["call.inter"])
         return dict(st["call.outs"])

@@ -932,6 +932,60 @@ typedef struct {
 size_t enerf_forward_composite_workspace_bytes(const enerf_composite_frame_args_t* args);
 int enerf_forward_composite(const enerf_composite_frame_args_t* args, enerf_stream_t stream);
 
+/* ---- source-view cache of the composite network (ABI v11 grew by these six entries; new symbols only, the version number is unchanged) ----
+ * Both FeatureNets of a composite frame read src_inps and neither depends on the target camera, so a viewer that draws many
+ * cameras from one rig of V views per time frame runs them once per time frame (enerf_composite_cache_build) and every frame
+ * gathers the selected views' blocks by a device-resident index instead (enerf_forward_composite_cached): bit-identical to
+ * enerf_forward_composite on the same views gathered by hand.
+ *   enerf_composite_cache_t   caller-owned, 16-byte-aligned device buffers for V views; per net (fg = feature_net, bg = feature_net_bg)
+ *       only what a composite frame reads: *_feat[i] (V,h_i,w_i,C_i), the channels-last feature map of level i for every cascade
+ *       level i < cas.num (the cost volumes' inputs), and *_tex[i] (V,Hr_i,Wr_i,TEX_i), the enerf_pack_texels_cl image of every
+ *       rendered level i — the foreground's with src_inps' colours, the background's with bg_src_inps'.  NULL = not needed: a
+ *       feature map that no cost volume reads (level_2 with two levels) is neither stored nor gathered.  exts (V,4,4), ixts (V,3,3).
+ *   enerf_composite_cache_sizes   floats per buffer, 0 = not needed: floats[0..2] = fg_feat, [3..5] = fg_tex, [6..8] = bg_feat,
+ *       [9..11] = bg_tex, [12] = exts, [13] = ixts.
+ *   enerf_composite_cache_build   src_inps / bg_src_inps (V,3,H,W) in [-1,1], exts (V,4,4), ixts (V,3,3): per net the FeatureNet
+ *       (both over src_inps) and the texel packs of the frame, over the views in chunks of `chunk` images (1..4; 0 = 4); the maps
+ *       the cache does not keep live in the workspace (enerf_composite_cache_build_workspace_bytes(H, W), whatever V is) for the
+ *       length of their chunk; copies the cameras.  Only enqueues.
+ *   enerf_composite_prep_indexed  enerf_composite_prep with the source cameras behind a device-side index: args->src_exts /
+ *       src_ixts are (V,4,4) / (V,3,3) tables, source camera s is row view_idx[s] (view_idx (S) int32 on the device); the same
+ *       launch writes the gathered rows to cam_exts (1,S,4,4) / cam_ixts (1,S,3,3).  Every output holds the bits of
+ *       enerf_composite_prep on those rows; an index outside [0,V) is never used as an address: that camera's rows and projection
+ *       matrices are NaN.  Further ENERF_EINVAL: view_idx / cam_exts / cam_ixts NULL, V < 1.
+ *   enerf_forward_composite_cached   enerf_forward_composite with both nets' maps, the texels and the source cameras taken from the
+ *       cache: view_idx (S) int32 in DEVICE memory (e.g. enerf_select_views' output), never read on the host.  args->src_inps,
+ *       bg_src_inps, src_exts, src_ixts and the two feature_net*_packed are ignored; outputs, options, streams and refusals are
+ *       enerf_forward_composite's.  The indexed preparation runs on the caller's stream in front of the fork; the sources are two
+ *       gather launches, the foreground's where feature_net ran, the background's on the caller's stream; from the cascades on
+ *       the frame is enerf_forward_composite's.  An index outside [0,V) is never used as an address: that view's cameras, maps
+ *       and texels become NaN, and so does every output (rgb .. z_vals) of the frame: the preparation leaves a flag in the
+ *       workspace and the level's enerf_composite_layers launch writes NaN (the NaN of the view alone would stop at the ReLUs
+ *       of the cost regularisation and reach the colours only; depth_map / std_map are not covered).  Further ENERF_EINVAL, nothing launched, the message naming the field: a NULL
+ *       cache, V < 1, H or W differing from the frame's, a missing feature map for a level < cas.num, a missing texel image for a
+ *       rendered level, unaligned buffers, a NULL view_idx.  workspace: enerf_forward_composite_cached_workspace_bytes (0 +
+ *       enerf_last_error() on invalid arguments); no FeatureNet scratch in it. */
+typedef struct {
+    float* fg_feat[ENERF_MAX_LEVELS];
+    float* fg_tex[ENERF_MAX_LEVELS];
+    float* bg_feat[ENERF_MAX_LEVELS];
+    float* bg_tex[ENERF_MAX_LEVELS];
+    float *exts, *ixts;
+    int V, H, W;
+} enerf_composite_cache_t;
+#define ENERF_COMPOSITE_CACHE_BUFFERS (4 * ENERF_MAX_LEVELS + 2)
+int enerf_composite_cache_sizes(const enerf_cascade_t* cas, int V, int H, int W, long long* floats);
+size_t enerf_composite_cache_build_workspace_bytes(int H, int W);
+int enerf_composite_cache_build(const enerf_composite_cache_t* cache, const float* src_inps, const float* bg_src_inps, const float* exts,
+                                const float* ixts, const float* feature_net_packed, const float* feature_net_bg_packed,
+                                const enerf_cascade_t* cas, int chunk, void* workspace, size_t workspace_bytes,
+                                const enerf_options_t* options, enerf_stream_t stream);
+int enerf_composite_prep_indexed(const enerf_composite_prep_t* args, const int* view_idx, int V, float* cam_exts, float* cam_ixts,
+                                 enerf_stream_t stream);
+size_t enerf_forward_composite_cached_workspace_bytes(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* cache);
+int enerf_forward_composite_cached(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* cache, const int* view_idx,
+                                   enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
