@@ -248,7 +248,13 @@ size_t enerf_cost_reg_workspace_bytes(int full, int B, int D, int h, int w) {
 int enerf_cost_reg(const float* packed, int in_channels, int full, const float* vol, int B, int D, int h, int w,
                    float* feat, float* prob, void* workspace, size_t workspace_bytes, const enerf_options_t* options,
                    enerf_stream_t stream) {
+    REQUIRE(feat, "cost_reg: null pointer");
     return cost_reg_run(packed, in_channels, full, vol, 0, B, D, h, w, feat, prob, workspace, workspace_bytes, options,
+                        (hipStream_t)stream);
+}
+int enerf_cost_reg_prob(const float* packed, int in_channels, int full, const float* vol, int B, int D, int h, int w, float* prob,
+                        void* workspace, size_t workspace_bytes, const enerf_options_t* options, enerf_stream_t stream) {
+    return cost_reg_run(packed, in_channels, full, vol, 0, B, D, h, w, nullptr, prob, workspace, workspace_bytes, options,
                         (hipStream_t)stream);
 }
 }  // extern "C"
@@ -256,10 +262,14 @@ namespace enerf {
 bool cost_reg_conv0_planar(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w) {
     return cost_reg_plan(in_channels, full, B, D, h, w, o, device_cu_count()).vol_planar_ok;
 }
+bool cost_reg_feat_optional(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w) {
+    const CostRegPlan P = cost_reg_plan(in_channels, full, B, D, h, w, o, device_cu_count());
+    return conv3d_route_optional_out(P.route[P.n - 1]);
+}
 int cost_reg_run(const float* packed, int in_channels, int full, const float* vol, int vol_planar, int B, int D, int h, int w,
                  float* feat, float* prob, void* workspace, size_t workspace_bytes, const enerf_options_t* options,
                  hipStream_t st, const CostRegHook* hook) {
-    REQUIRE(packed && vol && feat && prob && workspace, "cost_reg: null pointer");
+    REQUIRE(packed && vol && prob && workspace, "cost_reg: null pointer");
     REQUIRE(in_channels == 8 || in_channels == 16 || in_channels == 32, "cost_reg: in_channels=%d unsupported (8/16/32)",
             in_channels);
     REQUIRE(B > 0 && D > 0 && h > 0 && w > 0, "cost_reg: bad shape");
@@ -268,6 +278,8 @@ int cost_reg_run(const float* packed, int in_channels, int full, const float* vo
     if (workspace_bytes < enerf_cost_reg_workspace_bytes(full, B, D, h, w))
         return fail(ENERF_EWORKSPACE, "cost_reg: workspace too small");
     const CostRegPlan P = cost_reg_plan(in_channels, full, B, D, h, w, resolve_options(options), device_cu_count());
+    if (feat == nullptr && !conv3d_route_optional_out(P.route[P.n - 1]))
+        return fail(ENERF_EINVAL, "cost_reg: the heads' kernel at this shape and these options cannot skip the feature output (needs the batched-4x4 heads, conv3d_b4 != 1)");
     if (vol_planar && !P.vol_planar_ok)
         return fail(ENERF_EINVAL, "cost_reg: a quad-planar volume needs the asynchronously staged conv0 kernel (conv3d_b4 0/2, D % 4 == 0, >= conv3d_lds_min_voxels)");
     float* buf[kNumBufs] = {};

@@ -754,6 +754,9 @@ Conv3dRoute conv3d_route(const Conv3dLayer& L, bool has_residual, bool has_out2,
 }
 bool conv3d_route_planar_in(const Conv3dRoute& r) { return r.family == kRouteB4g || r.family == kRouteB4c; }
 bool conv3d_route_planar_out(const Conv3dRoute& r) { return r.family == kRouteT2All && r.cout == 8; }
+bool conv3d_route_optional_out(const Conv3dRoute& r) {
+    return r.heads && (r.family == kRouteB4 || r.family == kRouteB4g || r.family == kRouteB4c);
+}
 void conv3d_route_name(const Conv3dRoute& r, char* buf, size_t cap) {
     const char* tf = r.heads ? "true" : "false";
     switch (r.family) {

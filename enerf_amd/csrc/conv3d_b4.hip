@@ -101,6 +101,9 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4(const float* __restrict
     const float* lbase = lds + ((zl * HY + yl) * HX + xl) * 4;
     const float* wbase = wlds + li * 4;                            // row i = lane & 3 of every block: 4 addresses per wave
 
+    // heads with out == nullptr: nobody reads the eight feature channels (conv3d_b4_depth_only below) — skip their MFMAs and
+    // stores behind a block-uniform branch; the dacc chain is untouched
+    const bool feat = !HEADS || out != nullptr;
 #pragma unroll 1
     for (int cb = 0; cb < NCB; ++cb) {
         if (cb > 0) __syncthreads();
@@ -183,6 +186,7 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4(const float* __restrict
             }
 #pragma unroll
             for (int q = 0; q < QV; ++q) {
+                if (!feat) break;
                 const float4 A0 = aq[tap & 1][q][0], A1 = aq[tap & 1][q][1];
                 const float a0[4] = {A0.x, A0.y, A0.z, A0.w}, a1[4] = {A1.x, A1.y, A1.z, A1.w};
 #pragma unroll
@@ -208,7 +212,7 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4(const float* __restrict
         if (z >= D) continue;
         const long long o = (((long long)b * D + z) * H + y) * W + x;
 #pragma unroll
-        for (int half = 0; half < 2; ++half) {
+        for (int half = 0; half < 2 && feat; ++half) {
             float yv[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -233,11 +237,104 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4(const float* __restrict
 // =====================================================================================================================
 __device__ float g_b4_zeros[64];                                  // source of the zero padding (a lane's 16 bytes)
 
+// The fused heads of a cascade level nobody renders.  Only the render kernel samples the eight feature channels, so the frame
+// passes out == nullptr for such a level and the heads kernels below (b4g and b4c; a kernel argument, hence one block-uniform
+// branch at their top) run this body instead of their own: the same boxes, the same asynchronous staging — b4c's buffers, the box
+// plane + one chunk of the depth head's [tap][4] weights per pass, which fits either kernel's LDS — and the same dacc chain in the
+// same order, so prob keeps its bits; no feature weights, MFMAs or stores.  27 x 8 FMAs per pass and lane are left: the kernel is as
+// long as its staging.
+template <int CIN, int BD>
+__device__ __forceinline__ void conv3d_b4_depth_only(const float* __restrict__ wb4, const float* __restrict__ scale,
+                                                     const float* __restrict__ shift, const float* __restrict__ in,
+                                                     float* __restrict__ out2, int D, int H, int W, int nbd, int nbh, int nbw,
+                                                     int in_planar) {
+    constexpr int BH = 8, BW = 16, V = BD / 2;
+    constexpr int NQ = CIN / 4;
+    constexpr int HX = BW + 2, HY = BH + 2, HZ = BD + 2, NVOX = HZ * HY * HX;
+    constexpr int NCH = (NVOX + 63) / 64, PLANE = NCH * 64 * 4, BUF = PLANE + 256, MYCH = (NCH + 3) / 4;
+    ENERF_DYN_SMEM(float, lds);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = lane & 31;
+    const bool g1 = (m >= 4 && m < 12) || (m >= 16 && m < 20) || m >= 28;
+    const int xl = g1 ? (m < 12 ? m - 4 : m < 20 ? m - 8 : m - 16) : (m < 4 ? m : m < 16 ? m - 8 : m - 12);
+    const int yl = 4 * (wv & 1) + 2 * (lane >> 5) + (g1 ? 1 : 0), zl = wv >> 1;
+    int t = (int)xcd_contiguous(blockIdx.x, gridDim.x);
+    const int bw = t % nbw; t /= nbw;
+    const int bh = t % nbh; t /= nbh;
+    const int bd = t % nbd;
+    const int b = t / nbd;
+    const int x0 = bw * BW, y0 = bh * BH, z0 = bd * BD;
+    const float* inb = in + (long long)b * D * H * W * CIN;
+    const long long vstride = in_planar ? 4 : CIN, qstride = in_planar ? (long long)D * H * W * 4 : 4;
+
+    long long src_off[MYCH];                                       // element offset of the voxel (channel 0), or -1: zeros
+#pragma unroll
+    for (int k = 0; k < MYCH; ++k) {
+        const int v = (wv + 4 * k) * 64 + lane;
+        const int dz = v / (HY * HX), r2 = v - dz * (HY * HX), dy = r2 / HX, dx = r2 - dy * HX;
+        const int gx = x0 + dx - 1, gy = y0 + dy - 1, gz = z0 + dz - 1;
+        const bool ok = v < NVOX && gx >= 0 && gx < W && gy >= 0 && gy < H && gz >= 0 && gz < D;
+        src_off[k] = ok ? (((long long)gz * H + gy) * W + gx) * vstride : -1;
+    }
+    const int wd_off = ((lane < 27 ? lane : 26) * NQ * 3 + 2) * 16;   // b4 image: [tap][cq][slot 2][row 0][r]
+    auto issue = [&](int cq, float* buf) {
+#pragma unroll
+        for (int k = 0; k < MYCH; ++k)
+            if (wv + 4 * k < NCH)                                  // wave-uniform
+                glds16(src_off[k] >= 0 ? inb + src_off[k] + cq * qstride : g_b4_zeros, buf + (wv + 4 * k) * 256, lane);
+        if (wv == (NCH & 3)) glds16(wb4 + wd_off + cq * 48, buf + PLANE, lane);
+    };
+
+    float dacc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) dacc[v] = 0.f;
+    issue(0, lds);
+#pragma unroll 1
+    for (int cq = 0; cq < NQ; ++cq) {
+        float* buf = lds + (cq & 1) * BUF;
+        glds_wait_all();                                           // this wave's copies of pass cq have landed
+        block_barrier_raw();                                       // everyone's have; everyone is done reading the other buffer
+        if (cq + 1 < NQ) issue(cq + 1, lds + ((cq + 1) & 1) * BUF);
+        const float* lbase = buf + ((zl * HY + yl) * HX + xl) * 4;
+        const float* wdl = buf + PLANE;
+#pragma unroll
+        for (int tap = 0; tap < 27; ++tap) {
+            const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+            const float4 wd = *reinterpret_cast<const float4*>(wdl + tap * 4);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const float4 bb = *reinterpret_cast<const float4*>(lbase + (((2 * v + kd) * HY + kh) * HX + kw) * 4);
+                dacc[v] = __builtin_fmaf(wd.x, bb.x, dacc[v]);
+                dacc[v] = __builtin_fmaf(wd.y, bb.y, dacc[v]);
+                dacc[v] = __builtin_fmaf(wd.z, bb.z, dacc[v]);
+                dacc[v] = __builtin_fmaf(wd.w, bb.w, dacc[v]);
+            }
+        }
+    }
+
+    const int x = x0 + xl, y = y0 + yl;
+    if (x >= W || y >= H) return;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const int z = z0 + zl + 2 * v;
+        if (z >= D) continue;
+        out2[(((long long)b * D + z) * H + y) * W + x] = dacc[v] * scale[8] + shift[8];
+    }
+}
+
 template <int CIN, int BD, bool HEADS>
 __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4g(const float* __restrict__ wb4, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, const float* __restrict__ in,
                                                           float* __restrict__ out, float* __restrict__ out2, int relu, int B,
                                                           int D, int H, int W, int nbd, int nbh, int nbw, int in_planar) {
+    if constexpr (HEADS) {
+        if (out == nullptr) {                                      // depth head only (block-uniform)
+            if (out2 != nullptr) conv3d_b4_depth_only<CIN, BD>(wb4, scale, shift, in, out2, D, H, W, nbd, nbh, nbw, in_planar);
+            return;
+        }
+    }
     constexpr int BH = 8, BW = 16, V = BD / 2;
     constexpr int NQ = CIN / 4, NS = HEADS ? 3 : 2;
     constexpr int HX = BW + 2, HY = BH + 2, HZ = BD + 2, NVOX = HZ * HY * HX;
@@ -382,6 +479,12 @@ __global__ __launch_bounds__(256, 3) void k_conv3d_s1_b4c(const float* __restric
                                                           const float* __restrict__ shift, const float* __restrict__ in,
                                                           float* __restrict__ out, float* __restrict__ out2, int relu, int B,
                                                           int D, int H, int W, int nbd, int nbh, int nbw, int in_planar) {
+    if constexpr (HEADS) {
+        if (out == nullptr) {                                      // depth head only (block-uniform)
+            if (out2 != nullptr) conv3d_b4_depth_only<CIN, BD>(wb4, scale, shift, in, out2, D, H, W, nbd, nbh, nbw, in_planar);
+            return;
+        }
+    }
     constexpr int BH = 8, BW = 16, V = BD / 2;
     constexpr int NQ = CIN / 4;
     constexpr int HX = BW + 2, HY = BH + 2, HZ = BD + 2, NVOX = HZ * HY * HX;

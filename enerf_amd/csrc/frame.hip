@@ -197,6 +197,7 @@ struct LevelPlan {
     int D, h, w, C, Hs, Ws;            // volume extent; cost-volume feature channels and source-map size
     int Hr, Wr, render, masked, F, Ns; // render extent, flags, nerf feature width (C_f + 3), samples per ray
     int fl, from_l2;                   // rendered levels: the feature level of the texels; the texels ARE the level-2 map
+    int prob_only;                     // not rendered and the heads' kernel can skip it: no feature volume (no feat3d slot either)
     long long n_rays;
     // workspace offsets (floats)
     size_t proj, dv, nf, vol, feat3d, prob, depth, std, dmvs, tex, rays;
@@ -257,7 +258,11 @@ int make_plan(const enerf_frame_args_t* a, FramePlan* P, bool cached = false) {
         L.dv = take((size_t)nv);
         L.nf = take((size_t)a->B * 2 * L.h * L.w);
         L.vol = take((size_t)nv * L.C);
-        L.feat3d = take((size_t)nv * 8);
+        // only a render samples the level's 8-channel feature volume: where the fused heads can leave it out, an unrendered level
+        // neither computes nor holds it (enerf_options_t.heads_keep_feat = 1: the A/B)
+        L.prob_only = !c.render_if[i] && !(a->options && a->options->heads_keep_feat) &&
+                      cost_reg_feat_optional(resolve_options(a->options), L.C, i != 0, a->B, L.D, L.h, L.w);
+        if (!L.prob_only) L.feat3d = take((size_t)nv * 8);
         L.prob = take((size_t)nv);
         L.depth = take((size_t)a->B * L.h * L.w);
         L.std = take((size_t)a->B * L.h * L.w);
@@ -615,8 +620,8 @@ struct FrameRun {
         if (gated_here) {
             if (gate_mode == 3) enqueue_stage2(); else hk = &hook;
         }
-        int rc = cost_reg_run(a->cost_reg_packed[i], L.C, i != 0, ws + L.vol, vol_planar, a->B, L.D, L.h, L.w, ws + L.feat3d, ws + L.prob,
-                              ws + P.costreg_ws, P.costreg_ws_bytes, a->options, st, hk);
+        int rc = cost_reg_run(a->cost_reg_packed[i], L.C, i != 0, ws + L.vol, vol_planar, a->B, L.D, L.h, L.w,
+                              L.prob_only ? nullptr : ws + L.feat3d, ws + L.prob, ws + P.costreg_ws, P.costreg_ws_bytes, a->options, st, hk);
         if (gated_here) enqueue_stage2();
         if (rc == ENERF_OK && stage2_rc != ENERF_OK) rc = stage2_rc;
         if (rc == ENERF_OK) mark(ENERF_STAGE_LEVEL(i, ENERF_STAGE_COST_REG));

@@ -54,7 +54,11 @@ void launch_feature_volume(const float* feat_nhwc, const float* proj, const floa
 // does conv0 of this cost-reg network read the volume as channel-quad planes? (the frame driver asks before the warp: the answer is
 // conv0's route in the plan cost_reg_run itself launches from, capi.hip cost_reg_plan)
 bool cost_reg_conv0_planar(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w);
+// may this cost-reg network run without its feature output (cost_reg_run with feat == nullptr)?  True when the fused heads' route in
+// the same plan is a kernel that skips the feature channels on a null pointer (conv3d_route_optional_out)
+bool cost_reg_feat_optional(const enerf_options_t& o, int in_channels, int full, int B, int D, int h, int w);
 // enerf_cost_reg with the volume layout made explicit (vol_planar = 1: channel-quad planes, see launch_feature_volume)
+// feat == nullptr: prob only — the heads skip the eight feature channels nobody will read (needs cost_reg_feat_optional)
 // hook: called on the host right after layer `after_layer` (0 = conv0) has been enqueued (enerf_forward uses it to start a
 // side-lane stage at that point of the chain); nullptr = none
 struct CostRegHook { void (*fn)(void* ctx); void* ctx; int after_layer; };
@@ -113,6 +117,7 @@ Conv3dRoute conv3d_route(const Conv3dLayer& L, bool has_residual, bool has_out2,
                          int cu_count);
 bool conv3d_route_planar_in(const Conv3dRoute& r);      // the kernel can read channel-quad planes (b4g / b4c)
 bool conv3d_route_planar_out(const Conv3dRoute& r);     // the kernel can write them (the paired t2_all)
+bool conv3d_route_optional_out(const Conv3dRoute& r);   // fused heads whose kernel takes out == nullptr: depth head only (b4 families)
 void conv3d_route_name(const Conv3dRoute& r, char* buf, size_t cap);
 
 // The per-file launchers: geometry only, the route has decided.

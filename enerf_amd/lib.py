@@ -47,7 +47,7 @@ class Options(C.Structure):
     _fields_ = [("conv3d_global_only", _i), ("conv3d_lds_min_voxels", _ll), ("conv3d_pk8", _i),
                 ("featnet_unfused", _i), ("featnet_smooth0_plain", _i), ("conv3d_b4", _i), ("single_stream", _i),
                 ("side_gate", _i), ("fuse_depth_prep", _i), ("conv3d_t2_variant", _i), ("conv3d_small_variant", _i),
-                ("render_precision", _i)]
+                ("render_precision", _i), ("heads_keep_feat", _i)]
 
     def __repr__(self):
         return "Options(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if getattr(self, n)) + ")"
@@ -237,6 +237,7 @@ _SIGNATURES = {
     "enerf_cost_reg_pack": (_i, [C.POINTER(CostRegRaw), _f, _f]),
     "enerf_cost_reg_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "enerf_cost_reg": (_i, [_f, _i, _i, _f, _i, _i, _i, _i, _f, _f, _f, C.c_size_t, C.POINTER(Options), _f]),
+    "enerf_cost_reg_prob": (_i, [_f, _i, _i, _f, _i, _i, _i, _i, _f, _f, C.c_size_t, C.POINTER(Options), _f]),
     "enerf_depth_regression": (_i, [_f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
     "enerf_build_rays": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f]),
     "enerf_nerf_packed_floats": (_ll, [_i]),
@@ -584,6 +585,18 @@ class EnerfLib:
                                             _ptr(prob), _ptr(workspace), workspace.numel() * 4, _opt(options),
                                             self.stream_of(vol)), "cost_reg")
         return feat, prob
+
+    def cost_reg_prob(self, packed, in_channels, full, vol, workspace=None, options=None, out=None):
+        """prob of ``cost_reg`` alone (``enerf_cost_reg_prob``): the fused heads skip the feature channels."""
+        B, D, h, w, _ = vol.shape
+        need = self.dll.enerf_cost_reg_workspace_bytes(int(full), B, D, h, w)
+        if workspace is None or workspace.numel() * 4 < need:
+            workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=vol.device)
+        prob = _out(out, (B, D, h, w), vol.device, "cost_reg_prob")
+        self._check(self.dll.enerf_cost_reg_prob(_ptr(packed), in_channels, int(full), _ptr(vol), B, D, h, w, _ptr(prob),
+                                                 _ptr(workspace), workspace.numel() * 4, _opt(options), self.stream_of(vol)),
+                    "cost_reg_prob")
+        return prob
 
     def depth_regression(self, prob, dv, depth_inv, out=None):
         B, D, h, w = prob.shape

@@ -95,6 +95,10 @@ typedef struct {
                                             adv_sigma: 1.3e-3), so it is an opt-in, not the default;
                                         3 = "bf16x6": three pieces, six MFMAs: fp32-level accuracy, measured SLOWER than the exact
                                             kernel (203 us: the operand splits are VALU work, which does not overlap the MFMAs) */
+    int heads_keep_feat;             /* enerf_forward / enerf_forward_cached: 0 (default) = a cascade level that is not rendered runs its
+                                        fused heads for prob only when their kernel can (enerf_cost_reg_prob) — nobody reads that
+                                        level's 8-channel feature volume, and the workspace does not hold it;
+                                        1 = every level computes and stores its feature volume (A/B, tests) */
 } enerf_options_t;
 
 /* ---- layout adapters at the PyTorch boundary (FeatureNet output is NCHW, network.py:58-67) ---- */
@@ -191,6 +195,11 @@ size_t enerf_cost_reg_workspace_bytes(int full, int B, int D, int h, int w);
 int enerf_cost_reg(const float* packed, int in_channels, int full, const float* vol, int B, int D, int h, int w,
                    float* feat, float* prob, void* workspace, size_t workspace_bytes, const enerf_options_t* options,
                    enerf_stream_t stream);
+/* The same network for prob alone: the fused heads skip the eight feature channels (their matrix instructions and stores); prob is
+ * bit-identical to enerf_cost_reg's.  Only where the heads run on the batched-4x4 kernels (the default from 16384 voxels, conv3d_b4
+ * != 1); ENERF_EINVAL otherwise. */
+int enerf_cost_reg_prob(const float* packed, int in_channels, int full, const float* vol, int B, int D, int h, int w, float* prob,
+                        void* workspace, size_t workspace_bytes, const enerf_options_t* options, enerf_stream_t stream);
 
 /* ---- depth_regression (utils.py:658-667) ---- */
 int enerf_depth_regression(const float* prob, const float* depth_values, int B, int D, int h, int w, int depth_inv,
