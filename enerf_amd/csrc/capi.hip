@@ -324,6 +324,20 @@ extern "C" long long emu_cost_reg_routes(int in_channels, int full, int B, int D
     if (buf != nullptr && cap > 0) memcpy(buf, t.data(), t.size() < (size_t)cap ? t.size() : (size_t)cap);
     return (long long)t.size();
 }
+// emulator build only (tests/test_wgrad_routes.py): the route of one weight gradient as text — "name<template values>", then
+// key=value lines for scratch_bytes, atomic, second_stage, blocks, cols, chunks, tiles_a, tiles_b, tiles_y, tiles_x; launches nothing.
+// shape: the 20 fields of WgradShape in order.  Returns the length.
+extern "C" long long emu_wgrad_route(const int* shape, int a16, int b16, long long workspace_bytes, int cu_count, char* buf, long long cap) {
+    const int* s = shape;
+    const WgradShape p = {s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], s[13], s[14], s[15], s[16], s[17], s[18], s[19] != 0};
+    const WgradRoute r = wgrad_route(p, a16 != 0, b16 != 0, (size_t)workspace_bytes, cu_count);
+    char name[64], text[512];
+    wgrad_route_name(r, name, sizeof(name));
+    const int n = snprintf(text, sizeof(text), "%s\nscratch_bytes=%zu\natomic=%d\nsecond_stage=%s\nblocks=%d\ncols=%d\nchunks=%d\ntiles_a=%d\ntiles_b=%d\ntiles_y=%d\ntiles_x=%d\n",
+                           name, r.scratch_bytes, (int)r.atomic, wgrad_route_second_stage(r), r.blocks, r.cols, r.chunks, r.tiles_a, r.tiles_b, r.tiles_y, r.tiles_x);
+    if (buf != nullptr && cap > 0) memcpy(buf, text, n < cap ? n : cap);
+    return n;
+}
 #endif
 extern "C" {
 

@@ -173,6 +173,49 @@ inline Conv3dDesc conv3d_desc(const float* p, const Conv3dImage& im, int cin, in
 bool launch_conv3d(const Conv3dDesc& L, const Conv3dRoute& r, const float* in, const float* residual, float* out, float* out2, int B,
                    int Di, int Hi, int Wi, hipStream_t st);
 
+// ---- wgrad.hip ----------------------------------------------------------------------------------
+// One weight gradient dW[a][b][taps] = sum over the positions of the A grid (include/enerf_hip.h: enerf_conv_wgrad; enerf_gemm_wgrad
+// is the 1x1x1 problem on a 1 x 1 x P grid with row strides).
+struct WgradShape {
+    int n, Da, Ha, Wa, Ca;      // A grid (the positions summed over) and channels
+    int Db, Hb, Wb, Cb;         // B grid and channels
+    int lda, ldb;               // floats between consecutive positions of A / B (>= Ca / Cb)
+    int kd, kh, kw, stride, pad_d, pad_h, pad_w;
+    int bias;                   // 1: also dbias[a] = sum over the positions of A[a] (a virtual all-ones column Cb of B)
+    bool linear;                // enerf_gemm_wgrad's problem: k_gemm_wgrad whenever its tiles fit, in every A/B build
+};
+// Which kernel a weight gradient runs, as conv3d_route above: wgrad_route decides from values alone (no HIP call, no pointer, no static
+// state), the launcher in wgrad.hip launches what it decided, second stage included.  The upper-case fields are the template values of
+// the instantiation under the kernels' own names; wgrad_route_name prints them in template order: wgrad2d_3x3_p16<1,2>,
+// conv_wgrad<3,3,3,3,2>, gemm_wgrad<2,3>.
+enum WgradFamily {
+    kWgradNone = 0,     // no kernel handles the kernel extents
+    kWgradGemm,         // k_gemm_wgrad<TA, TB>: 1x1x1 stride 1, <= 4 x 6 channel tiles; second stage k_wgrad_reduce
+    kWgrad2dC8,         // k_wgrad2d_3x3_c8<A4, B4, NCB>: 1x3x3 stride 1, <= 8 A channels; second stage k_colsum
+    kWgrad2dP16,        // k_wgrad2d_3x3_p16<NA, NB>: ... 16 / 32 channels on both sides; k_colsum
+    kWgrad3dC8,         // k_wgrad3d_c8<A4, NCB>: 3x3x3 stride 1, <= 8 channels on one side (swapped: on the B side); k_colsum
+    kWgradGeneric       // k_conv_wgrad<KD, KH, KW, SPLIT, PL>: everything else; k_wgrad_reduce
+};
+struct WgradRoute {
+    int family = kWgradNone;
+    int TA = 0, TB = 0;                                 // k_gemm_wgrad
+    bool A4 = false, B4 = false;                        // c8 kernels: 16-byte (true) or scalar staging of the A / B tile
+    int NCB = 0, NA = 0, NB = 0;                        // c8: blocks of 8 B channels per launch column; p16: 16-channel blocks of A / B
+    bool swapped = false;                               // k_wgrad3d_c8: the kernel's A is the caller's B (the <= 8-channel side)
+    int KD = 0, KH = 0, KW = 0, SPLIT = 0, PL = 0;      // k_conv_wgrad
+    int blocks = 0, cols = 1;                           // first stage's grid (x, y); y = 2: the two halves of a 32-channel B (3-D)
+    int chunks = 0;                                     // partial results per output element: what the second stage sums
+    int tiles_a = 0, tiles_b = 0;                       // gemm / generic: 16-channel tiles of A and of B (+ bias column)
+    int tiles_y = 0, tiles_x = 0;                       // tile kernels: image tiles per plane
+    size_t scratch_bytes = 0;                           // bytes of the caller's workspace the two stages use
+    bool atomic = false;                                // gemm / generic with a workspace below their two-stage form: no second stage,
+                                                        // fp32 atomics onto a grad_w (and grad_bias) the caller zeroes first
+};
+// a16 / b16: the A / B base address is 16-byte aligned.  workspace_bytes: 0 without a workspace.
+WgradRoute wgrad_route(const WgradShape& p, bool a16, bool b16, size_t workspace_bytes, int cu_count);
+void wgrad_route_name(const WgradRoute& r, char* buf, size_t cap);
+const char* wgrad_route_second_stage(const WgradRoute& r);     // "wgrad_reduce", "colsum" or "" (atomic commit)
+
 // ---- conv2d.hip (FeatureNet) ----------------------------------------------------------------------
 struct Conv2dDesc {
     const float* w;        // packed A operands

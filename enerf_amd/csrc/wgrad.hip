@@ -19,6 +19,7 @@
 // the block adds its partial tile set to dW with fp32 atomics.  Out-of-range taps (padding) and channels >= C load zeros.
 #include "kernels.h"
 
+// ---- tunables: every one an A/B build switch (tools/ compiles this file with -D...), the default is what was measured best ----
 #ifndef ENERF_WGRAD_PREFETCH
 #define ENERF_WGRAD_PREFETCH 1            /* tiled 2-D kernel: the next tile's global loads are issued before this tile's MFMAs */
 #endif
@@ -27,6 +28,39 @@
 #endif
 #ifndef ENERF_WGRAD_REDUCE_8
 #define ENERF_WGRAD_REDUCE_8 1            /* k_wgrad_reduce: eight (1) or four (0) loads in flight per thread */
+#endif
+#ifndef ENERF_WGRAD_PITCH32
+#define ENERF_WGRAD_PITCH32 1             /* 0: the tile kernels' first LDS pitches (right for 64 banks, 2-way conflicts with 32) */
+#endif
+// measured (MI355X, config-5 shapes, tools/gpu_wgrad_variants.sh): the tap split wins on the layers with few positions
+// (<= 10k: 32 -> 16-20 us) and loses from 82k positions on (three waves re-read every A value and row), which keep one
+// wave per group
+#ifndef ENERF_WGRAD_SPLIT_BELOW
+#define ENERF_WGRAD_SPLIT_BELOW 50000     /* 0 = never split 3x3(x3), a huge value = always */
+#endif
+#ifndef ENERF_WGRAD2D_TILE
+#define ENERF_WGRAD2D_TILE 1              /* 0: the 3x3 stride-1 2-D layers stay on k_conv_wgrad */
+#endif
+#ifndef ENERF_WGRAD2D_P16
+#define ENERF_WGRAD2D_P16 1               /* 0: the 16 / 32-channel 3x3 layers stay on k_conv_wgrad */
+#endif
+#ifndef ENERF_WGRAD2D_BPC
+#define ENERF_WGRAD2D_BPC 4               /* k_wgrad2d_3x3_c8<*, *, 1>: persistent blocks per CU (112 VGPRs: four waves per SIMD; 21 KB of LDS each) */
+#endif
+#ifndef ENERF_WGRAD3D_TILE
+#define ENERF_WGRAD3D_TILE 1              /* 0: the 3x3x3 stride-1 layers stay on k_conv_wgrad */
+#endif
+#ifndef ENERF_WGRAD_1X1_GEMM
+#define ENERF_WGRAD_1X1_GEMM 1            /* 0: 1x1 conv layers stay on k_conv_wgrad<1,1,1> (enerf_gemm_wgrad keeps the GEMM) */
+#endif
+#ifndef ENERF_GW_UNROLL
+#define ENERF_GW_UNROLL 1                 /* k_gemm_wgrad: 0 = one row group per iteration (round 5) */
+#endif
+#ifndef ENERF_GW_INFLIGHT
+#define ENERF_GW_INFLIGHT 16              /* ... operand registers requested per iteration (x 256 B per wave in flight) */
+#endif
+#ifndef ENERF_GW_BLOCKS_PER_CU
+#define ENERF_GW_BLOCKS_PER_CU 4          /* measured: 2 -> 4 blocks per CU 9.92 -> 9.82 ms per training step */
 #endif
 
 namespace enerf {
@@ -324,64 +358,6 @@ static void reduce_flush(hipStream_t st) {
     g_reduce_deferring = false;
 }
 
-template <int KD, int KH, int KW, int SPLIT, int PL>
-static void launch_wgrad_k(const float* A, const float* Bt, const WgradGeom& q, float* dW, float* dbias, float* scratch, hipStream_t st) {
-    const unsigned grid = (unsigned)(q.tiles_a * q.tiles_b * q.chunks);
-    ENERF_LAUNCH((k_conv_wgrad<KD, KH, KW, SPLIT, PL>), grid, SPLIT * PL * 64, 0, st, A, Bt, q, dW, dbias, scratch);
-    if (scratch != nullptr)
-        launch_wgrad_reduce(scratch, q.tiles_a * q.tiles_b, q.chunks, KD * KH * KW, q.tiles_b, q.Ca, q.Cb, q.bias, 0, dW, dbias, st);
-}
-// position lanes per block for a kernel shape (the tap split is the leading kernel dimension; 1x1x1: four position lanes)
-// measured (MI355X, config-5 shapes, tools/gpu_wgrad_variants.sh): the tap split wins on the layers with few positions
-// (<= 10k: 32 -> 16-20 us) and loses from 82k positions on (three waves re-read every A value and row), which keep one
-// wave per group
-#ifndef ENERF_WGRAD_SPLIT_BELOW
-#define ENERF_WGRAD_SPLIT_BELOW 50000           /* A/B builds: 0 = never split 3x3(x3), a huge value = always */
-#endif
-static bool wgrad_split(int taps, long long npos) { return taps == 25 || ((taps == 27 || taps == 9) && npos < (long long)ENERF_WGRAD_SPLIT_BELOW); }
-static int wgrad_pl(int taps, long long npos) { return taps == 25 ? 1 : (wgrad_split(taps, npos) ? 2 : 4); }
-// position chunks (= blocks per channel-tile pair): enough blocks to fill the chip, >= 8 position groups per wave
-static int wgrad_chunks(long long npos, int pairs, int taps, bool two_stage) {
-    const long long groups = cdivl(npos, 4);
-    long long want = (long long)device_cu_count() * (two_stage ? 2 : 4) / pairs;
-    if (want < 1) want = 1;
-    const long long maxc = cdivl(groups, wgrad_pl(taps, npos) * 8);
-    return (int)(want < maxc ? want : (maxc < 1 ? 1 : maxc));
-}
-#ifndef ENERF_WGRAD2D_BPC
-#define ENERF_WGRAD2D_BPC 4                      /* persistent blocks per CU (112 VGPRs: four waves per SIMD; 21 KB of LDS each) */
-#endif
-#ifndef ENERF_WGRAD2D_TILE
-#define ENERF_WGRAD2D_TILE 1                     /* 0: these layers stay on k_conv_wgrad (A/B builds) */
-#endif
-#ifndef ENERF_WGRAD3D_TILE
-#define ENERF_WGRAD3D_TILE 1
-#endif
-#ifndef ENERF_WGRAD_1X1_GEMM
-#define ENERF_WGRAD_1X1_GEMM 1                   /* 0: 1x1 layers stay on k_conv_wgrad<1,1,1> (A/B builds) */
-#endif
-size_t gemm_wgrad_workspace_bytes(long long P, int Ca, int Cb, int bias);
-bool launch_gemm_wgrad(const float* A, int lda, int Ca, const float* Bt, int ldb, int Cb, long long P, float* dW, float* dbias,
-                       hipStream_t st, void* workspace, size_t workspace_bytes);
-size_t conv_wgrad_workspace_bytes(long long npos, int Ca, int Cb, int taps, int bias) {
-    const int pairs = cdiv(Ca, 16) * cdiv(Cb + bias, 16);
-    const size_t two_stage = (size_t)pairs * wgrad_chunks(npos, pairs, taps, true) * taps * 256 * sizeof(float);
-    // k_wgrad2d_3x3_c8 (below): one compact row of Ca*Cb*9 sums per persistent block (the query does not know the grid: the bound)
-    const size_t tiled = (ENERF_WGRAD2D_TILE && taps == 9 && Ca <= 32 && Cb <= 32 && !bias)
-                             ? (size_t)device_cu_count() * (Ca <= 8 ? ENERF_WGRAD2D_BPC : 3) * Ca * Cb * 9 * sizeof(float) : 0;
-    // k_wgrad3d_c8: at most 2 blocks per CU in all, one row of the whole dW each
-    const size_t tiled3 = (ENERF_WGRAD3D_TILE && taps == 27 && !bias && ((Ca <= 8 && Cb <= 32) || (Ca == 16 && Cb <= 8)))
-                              ? (size_t)device_cu_count() * 2 * Ca * Cb * 27 * sizeof(float) : 0;
-    size_t t = two_stage > tiled ? two_stage : tiled;
-    t = t > tiled3 ? t : tiled3;
-    // a 1x1 stride-1 layer is a plain position-reduction GEMM (k_gemm_wgrad: all tile pairs in one wave, rows read once)
-    if (ENERF_WGRAD_1X1_GEMM && taps == 1 && cdiv(Ca, 16) <= 4 && cdiv(Cb + bias, 16) <= 6) {
-        const size_t gm = gemm_wgrad_workspace_bytes(npos, Ca, Cb, bias);
-        t = t > gm ? t : gm;
-    }
-    return t;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 5: the 3x3 stride-1 2-D layers with <= 8 gradient channels (FeatureNet conv0.0 3 -> 8, conv0.1 8 -> 8, smooth0 32 -> 8:
 // full resolution, 983k positions each at dtu_pretrain) from LDS tiles, three kernel rows per MFMA.
@@ -408,9 +384,6 @@ constexpr int kW2TH = 8, kW2TW = 32;
 // 64-bank model, a 2-way conflict on every operand read with 32: PMC counted SQ_LDS_BANK_CONFLICT at 0.42 - 0.55 of the LDS-active
 // cycles, profiles/r05_micro_wgrad_pmc.txt.)  The 8-lane groups of the ds_write_b128 staging stores cover one pixel's quads in
 // four channel planes: the plane stride ≡ 8 (mod 32) keeps those apart too.
-#ifndef ENERF_WGRAD_PITCH32
-#define ENERF_WGRAD_PITCH32 1                    /* 0: the first version's pitches (A/B builds) */
-#endif
 constexpr int kW2BCols = kW2TW + 2;
 constexpr int kW2APitch = kW2TW * 8 + (ENERF_WGRAD_PITCH32 ? 16 : 32), kW2BPitch = kW2BCols * 8 + (ENERF_WGRAD_PITCH32 ? 8 : 0);
 constexpr int kW2BPlane = (kW2TH + 2) * kW2BPitch + (ENERF_WGRAD_PITCH32 ? 8 : 0);
@@ -788,140 +761,6 @@ __global__ __launch_bounds__(256) void k_wgrad3d_c8(const float* __restrict__ A,
         __syncthreads();
     }
 }
-static int wgrad2d_bpc(int Ca, int Cb) {               // by LDS (21 / 32 / 54 KB per block; p16: 38 / 60 / 77 KB) and registers
-    if (Ca > 8) return Cb == 32 ? 1 : 3;                // (272 / 356 registers with a 32-channel B: one wave per SIMD)
-    return Cb <= 8 ? ENERF_WGRAD2D_BPC : Cb <= 16 ? 3 : 2;
-}
-static int wgrad2d_blocks(int n, int H, int W, int Ca, int Cb) {
-    const long long ntiles = (long long)n * cdiv(Ca > 8 ? H : H + 1, kW2TH) * cdiv(W, kW2TW);
-    const long long cap = (long long)device_cu_count() * wgrad2d_bpc(Ca, Cb);
-    return (int)(ntiles < cap ? ntiles : cap);
-}
-#ifndef ENERF_WGRAD2D_P16
-#define ENERF_WGRAD2D_P16 1                      /* 0: the 16 / 32-channel 3x3 layers stay on k_conv_wgrad (A/B builds) */
-#endif
-static bool wgrad2d_p16(int Ca, int Cb) { return ENERF_WGRAD2D_P16 && ((Ca == 16 && (Cb == 16 || Cb == 32)) || (Ca == 32 && Cb == 32)); }
-static bool wgrad2d_fits(int n, int Da, int Ha, int Wa, int Ca, int Db, int Hb, int Wb, int Cb, int kd, int kh, int kw, int stride,
-                         int pad_d, int pad_h, int pad_w, bool bias) {
-    const bool shape = (Ca <= 8 && (Cb <= 8 || Cb == 16 || Cb == 32)) || wgrad2d_p16(Ca, Cb);
-    return ENERF_WGRAD2D_TILE && kd == 1 && kh == 3 && kw == 3 && stride == 1 && pad_d == 0 && pad_h == 1 && pad_w == 1 && Da == 1 &&
-           Db == 1 && Ha == Hb && Wa == Wb && shape && !bias && (long long)n * Ha * Wa >= 2048;
-}
-static size_t wgrad2d_workspace_bytes(int n, int H, int W, int Ca, int Cb) {
-    return (size_t)wgrad2d_blocks(n, H, W, Ca, Cb) * Ca * Cb * 9 * sizeof(float);
-}
-static bool launch_wgrad2d(const float* A, const float* Bt, int n, int H, int W, int Ca, int Cb, int lda, int ldb, float* dW,
-                           float* scratch, hipStream_t st) {
-    const int blocks = wgrad2d_blocks(n, H, W, Ca, Cb), tiles_y = cdiv(H + 1, kW2TH), tiles_x = cdiv(W, kW2TW);
-    const unsigned abytes = (unsigned)((long long)n * H * W * lda * 4), bbytes = (unsigned)((long long)n * H * W * ldb * 4);   // (< 2^32: checked by the C entries)
-    if (Ca > 8) {                                          // 16 / 32 gradient channels: the plain tiles
-        if (lda % 4 != 0 || ldb % 4 != 0 || (((uintptr_t)A | (uintptr_t)Bt) & 15) != 0) return false;
-        const int ty16 = cdiv(H, kW2TH);
-#define ENERF_W2P(NA, NB) ENERF_LAUNCH((k_wgrad2d_3x3_p16<NA, NB>), (unsigned)blocks, 256, 0, st, A, Bt, n, H, W, lda, ldb, ty16, tiles_x, abytes, bbytes, scratch)
-        if (Ca == 32) ENERF_W2P(2, 2); else if (Cb == 32) ENERF_W2P(1, 2); else ENERF_W2P(1, 1);
-#undef ENERF_W2P
-        launch_colsum(scratch, blocks, Ca * Cb * 9, Ca * Cb * 9, 0, dW, cdiv(Ca * Cb * 9, 64), 1, st);
-        return true;
-    }
-    const bool a4 = (Ca == 4 || Ca == 8) && lda % 4 == 0 && ((uintptr_t)A & 15) == 0;
-    const bool b4 = (Cb == 4 || Cb == 8 || Cb == 16 || Cb == 32) && ldb % 4 == 0 && ((uintptr_t)Bt & 15) == 0;
-    if (Cb > 8 && !b4) return false;
-#define ENERF_W2(A4, B4, NCB) ENERF_LAUNCH((k_wgrad2d_3x3_c8<A4, B4, NCB>), (unsigned)blocks, 256, 0, st, A, Bt, n, H, W, Ca, Cb, lda, ldb, tiles_y, tiles_x, abytes, bbytes, scratch)
-    if (Cb == 32) { if (a4) ENERF_W2(true, true, 4); else ENERF_W2(false, true, 4); }
-    else if (Cb == 16) { if (a4) ENERF_W2(true, true, 2); else ENERF_W2(false, true, 2); }
-    else if (a4) { if (b4) ENERF_W2(true, true, 1); else ENERF_W2(true, false, 1); }
-    else { if (b4) ENERF_W2(false, true, 1); else ENERF_W2(false, false, 1); }
-#undef ENERF_W2
-    launch_colsum(scratch, blocks, Ca * Cb * 9, Ca * Cb * 9, 0, dW, cdiv(Ca * Cb * 9, 64), 1, st);
-    return true;
-}
-#ifndef ENERF_WGRAD3D_TILE
-#define ENERF_WGRAD3D_TILE 1                     /* 0: these layers stay on k_conv_wgrad (A/B builds) */
-#endif
-// normal: Ca <= 8 gradient channels, Cb = 8 / 16 / 32 input channels; swapped: Ca = 16, Cb <= 8 (the fused heads)
-static bool wgrad3d_fits(int n, int Da, int Ha, int Wa, int Ca, int Db, int Hb, int Wb, int Cb, int kd, int kh, int kw, int stride,
-                         int pad_d, int pad_h, int pad_w, bool bias) {
-    const bool shape = (Ca <= 8 && (Cb == 8 || Cb == 16 || Cb == 32)) || (Ca == 16 && Cb <= 8);
-    return ENERF_WGRAD3D_TILE && kd == 3 && kh == 3 && kw == 3 && stride == 1 && pad_d == 1 && pad_h == 1 && pad_w == 1 && Da == Db &&
-           Ha == Hb && Wa == Wb && shape && !bias && (long long)n * Da * Ha * Wa >= 32768;
-}
-static int wgrad3d_blocks(int n, int D, int H, int W, int cols) {
-    const long long ntiles = (long long)n * D * cdiv(H + 1, kW2TH) * cdiv(W, kW2TW);
-    const long long cap = (long long)device_cu_count() * 2 / cols;                   // 76 KB of LDS per block: two per CU
-    return (int)(ntiles < cap ? ntiles : (cap < 1 ? 1 : cap));
-}
-static size_t wgrad3d_workspace_bytes(int n, int D, int H, int W, int Ca, int Cb) {
-    const int cols = (Ca <= 8 && Cb == 32) ? 2 : 1;
-    return (size_t)cols * wgrad3d_blocks(n, D, H, W, cols) * Ca * (Cb / cols) * 27 * sizeof(float);
-}
-static bool launch_wgrad3d(const float* A, const float* Bt, int n, int D, int H, int W, int Ca, int Cb, int lda, int ldb, float* dW,
-                           float* scratch, hipStream_t st) {
-    const bool swapped = Ca > 8;
-    const float* Ak = swapped ? Bt : A;                    // the kernel's A' (<= 8 channels) and B' (8 or 16 per column)
-    const float* Bk = swapped ? A : Bt;
-    const int Cak = swapped ? Cb : Ca, ldak = swapped ? ldb : lda, ldbk = swapped ? lda : ldb;
-    const int Cbt = swapped ? Ca : Cb, cols = Cbt == 32 ? 2 : 1, Cbk = Cbt / cols;
-    if (ldbk % 4 != 0 || ((uintptr_t)Bk & 15) != 0) return false;
-    const bool a4 = (Cak == 4 || Cak == 8) && ldak % 4 == 0 && ((uintptr_t)Ak & 15) == 0;
-    const int blocks = wgrad3d_blocks(n, D, H, W, cols), tiles_y = cdiv(H + 1, kW2TH), tiles_x = cdiv(W, kW2TW);
-    const unsigned abytes = (unsigned)((long long)n * D * H * W * ldak * 4), bbytes = (unsigned)((long long)n * D * H * W * ldbk * 4);
-    const dim3 grid((unsigned)blocks, (unsigned)cols);
-#define ENERF_W3(A4, NCB) ENERF_LAUNCH((k_wgrad3d_c8<A4, NCB>), grid, 256, 0, st, Ak, Bk, n, D, H, W, Cak, Cbk, ldak, ldbk, tiles_y, tiles_x, swapped ? 1 : 0, abytes, bbytes, scratch)
-    if (Cbk == 16) { if (a4) ENERF_W3(true, 2); else ENERF_W3(false, 2); }
-    else { if (a4) ENERF_W3(true, 1); else ENERF_W3(false, 1); }
-#undef ENERF_W3
-    const int n_row = Cak * Cbk * 27;
-    launch_colsum(scratch, blocks, n_row, swapped ? n_row : Cbk * 27, Cbt * 27, dW, cdiv(n_row, 64), cols, st);
-    return true;
-}
-
-bool launch_conv_wgrad(const float* A, const float* Bt, int n, int Da, int Ha, int Wa, int Ca, int Db, int Hb, int Wb, int Cb,
-                       int kd, int kh, int kw, int stride, int pad_d, int pad_h, int pad_w, float* dW, hipStream_t st, int lda = 0,
-                       int ldb = 0, float* dbias = nullptr, void* workspace = nullptr, size_t workspace_bytes = 0) {
-    WgradGeom q;
-    q.bias = dbias != nullptr;
-    q.lda = lda > 0 ? lda : Ca; q.ldb = ldb > 0 ? ldb : Cb;
-    q.n = n; q.Da = Da; q.Ha = Ha; q.Wa = Wa; q.Ca = Ca; q.Db = Db; q.Hb = Hb; q.Wb = Wb; q.Cb = Cb;
-    q.stride = stride; q.pad_d = pad_d; q.pad_h = pad_h; q.pad_w = pad_w;
-    q.tiles_a = cdiv(Ca, 16); q.tiles_b = cdiv(Cb + q.bias, 16);
-    q.npos = (long long)n * Da * Ha * Wa;
-    q.abytes = (unsigned)(q.npos * q.lda * 4);                       // (< 2^32: checked by the C entries)
-    q.bbytes = (unsigned)((long long)n * Db * Hb * Wb * q.ldb * 4);
-    // 1x1(x1) stride-1 layers (FeatureNet toplayer / lat1 / lat0): k_conv_wgrad<1,1,1> decodes every position (three divisions per
-    // MFMA) and re-reads the rows once per tile pair (lat0 at full resolution: 108 us); as a GEMM over the positions the rows are
-    // read once and there is nothing to decode.  (enerf_gemm_wgrad falls back to this function for > 4 x 6 tiles: no recursion,
-    // that case fails the tile test here too.)
-    if (ENERF_WGRAD_1X1_GEMM && kd == 1 && kh == 1 && kw == 1 && stride == 1 && pad_d == 0 && pad_h == 0 && pad_w == 0 && Da == Db && Ha == Hb &&
-        Wa == Wb && cdiv(Ca, 16) <= 4 && cdiv(Cb + q.bias, 16) <= 6 && q.npos * (long long)(q.lda > q.ldb ? q.lda : q.ldb) < (1LL << 30) &&
-        launch_gemm_wgrad(A, q.lda, Ca, Bt, q.ldb, Cb, q.npos, dW, dbias, st, workspace, workspace_bytes))
-        return true;
-    if (wgrad2d_fits(n, Da, Ha, Wa, Ca, Db, Hb, Wb, Cb, kd, kh, kw, stride, pad_d, pad_h, pad_w, dbias != nullptr) && workspace != nullptr &&
-        workspace_bytes >= wgrad2d_workspace_bytes(n, Ha, Wa, Ca, Cb) &&
-        launch_wgrad2d(A, Bt, n, Ha, Wa, Ca, Cb, q.lda, q.ldb, dW, (float*)workspace, st))
-        return true;
-    if (wgrad3d_fits(n, Da, Ha, Wa, Ca, Db, Hb, Wb, Cb, kd, kh, kw, stride, pad_d, pad_h, pad_w, dbias != nullptr) && workspace != nullptr &&
-        workspace_bytes >= wgrad3d_workspace_bytes(n, Da, Ha, Wa, Ca, Cb) &&
-        launch_wgrad3d(A, Bt, n, Da, Ha, Wa, Ca, Cb, q.lda, q.ldb, dW, (float*)workspace, st))
-        return true;
-    const int taps = kd * kh * kw, pairs = q.tiles_a * q.tiles_b;
-    float* scratch = (workspace != nullptr && workspace_bytes >= conv_wgrad_workspace_bytes(q.npos, Ca, Cb, taps, q.bias)) ? (float*)workspace : nullptr;
-    q.chunks = wgrad_chunks(q.npos, pairs, taps, scratch != nullptr);
-    const bool split = wgrad_split(taps, q.npos);
-    if (kd == 3 && kh == 3 && kw == 3) {
-        if (split) launch_wgrad_k<3, 3, 3, 3, 2>(A, Bt, q, dW, dbias, scratch, st);       // wave = (kd, position lane)
-        else launch_wgrad_k<3, 3, 3, 1, 4>(A, Bt, q, dW, dbias, scratch, st);
-        return true;
-    }
-    if (kd == 1 && kh == 3 && kw == 3) {
-        if (split) launch_wgrad_k<1, 3, 3, 3, 2>(A, Bt, q, dW, dbias, scratch, st);       // wave = (kh, position lane)
-        else launch_wgrad_k<1, 3, 3, 1, 4>(A, Bt, q, dW, dbias, scratch, st);
-        return true;
-    }
-    if (kd == 1 && kh == 5 && kw == 5) { launch_wgrad_k<1, 5, 5, 5, 1>(A, Bt, q, dW, dbias, scratch, st); return true; }   // wave = kh
-    if (kd == 1 && kh == 1 && kw == 1) { launch_wgrad_k<1, 1, 1, 1, 4>(A, Bt, q, dW, dbias, scratch, st); return true; }
-    return false;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Linear-layer weight gradients: grad_w[a][b] = sum_p A[p][a] * B[p][b] with P up to ~2M rows and 1..89 columns per side.
 // k_conv_wgrad<1,1,1> gives every (16x16) tile pair its own blocks, so the rows of A are re-read tiles_b times and those
@@ -947,12 +786,6 @@ __device__ __forceinline__ void gemm_wgrad_body(const float* __restrict__ A, con
     // group; with one group per iteration and eight waves per CU the 1 x 1 .. 2 x 2 shapes (view_fc, fc, global_fc: most of the MLP's
     // layers) had 4 - 8 KB in flight per CU and streamed their operands at 1.7 - 2.5 TB/s (the 4 x 6 shape: 5.4).  The groups of a
     // wave are still accumulated in ascending order: same sums, bit for bit.
-#ifndef ENERF_GW_UNROLL
-#define ENERF_GW_UNROLL 1            // 0 (A/B): one row group per iteration (round 5)
-#endif
-#ifndef ENERF_GW_INFLIGHT
-#define ENERF_GW_INFLIGHT 16         // operand registers requested per iteration (x 256 B per wave in flight)
-#endif
     constexpr int UQ = ENERF_GW_INFLIGHT / (TA + TB);
     constexpr int U = !ENERF_GW_UNROLL ? 1 : (UQ < 1 ? 1 : (UQ > 8 ? 8 : UQ));
     const long long gstride = (long long)nblk * 4;
@@ -1087,55 +920,261 @@ __global__ __launch_bounds__(1024) void k_gemm_wgrad_group_reduce(GemmGroup G) {
     else if (d.bias && b_ch == d.Cb) d.dbias[a_ch] = v;
 }
 
-template <int TA>
-static bool launch_gemm_wgrad_ta(int tb, unsigned grid, hipStream_t st, const float* A, const float* Bt, int lda, int ldb, int Ca,
-                                 int Cb, int bias, long long P, float* dW, float* dbias, float* scratch) {
-#define ENERF_GW(TBV) case TBV: ENERF_LAUNCH((k_gemm_wgrad<TA, TBV>), grid, 256, 0, st, A, Bt, lda, ldb, Ca, Cb, bias, P, dW, dbias, scratch); return true;
-    switch (tb) { ENERF_GW(1) ENERF_GW(2) ENERF_GW(3) ENERF_GW(4) ENERF_GW(5) ENERF_GW(6) default: return false; }
-#undef ENERF_GW
+// ---------------------------------------------------------------------------------------------------------------------
+// Kernel selection: wgrad_route decides, launch_wgrad launches what it decided.  Every condition, grid size and workspace size
+// is one function here; the route calls it with the layer's geometry and the workspace queries, which see neither the grid nor
+// the stride, with the weakest arguments that geometry can have.
+// ---------------------------------------------------------------------------------------------------------------------
+// k_gemm_wgrad: a 1x1(x1) stride-1 layer (FeatureNet toplayer / lat1 / lat0) is a plain position-reduction GEMM.  k_conv_wgrad<1,1,1>
+// decodes every position (three divisions per MFMA) and re-reads the rows once per tile pair (lat0 at full resolution: 108 us); here
+// the rows are read once and there is nothing to decode.  All tile pairs live in one wave, so they must fit: <= 4 x 6 tiles.
+static bool gemm_reach(int kd, int kh, int kw, int Ca, int Cb, int bias, bool linear) {
+    return (linear || ENERF_WGRAD_1X1_GEMM) && kd == 1 && kh == 1 && kw == 1 && cdiv(Ca, 16) <= 4 && cdiv(Cb + bias, 16) <= 6;
 }
-static long long gemm_wgrad_blocks(long long P) {
-    const long long groups = cdivl(P, 4);
-    long long blocks = cdivl(groups, 4 * 16);                         // >= 16 row groups per wave
-#ifndef ENERF_GW_BLOCKS_PER_CU
-#define ENERF_GW_BLOCKS_PER_CU 4       // measured: 2 -> 4 blocks per CU 9.92 -> 9.82 ms per training step
-#endif
-    const long long cap = (long long)device_cu_count() * ENERF_GW_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : blocks;
+static long long gemm_wgrad_blocks(long long P, int cu_count) {
+    const long long blocks = cdivl(cdivl(P, 4), 4 * 16);              // >= 16 row groups per wave
+    const long long cap = (long long)cu_count * ENERF_GW_BLOCKS_PER_CU;
+    return blocks > cap ? cap : (blocks < 1 ? 1 : blocks);
 }
-size_t gemm_wgrad_workspace_bytes(long long P, int Ca, int Cb, int bias) {
-    const int ta = cdiv(Ca, 16), tb = cdiv(Cb + bias, 16);
-    if (ta > 4 || tb > 6) return conv_wgrad_workspace_bytes(P, Ca, Cb, 1, bias);      // the k_conv_wgrad<1,1,1> fallback
-    return (size_t)gemm_wgrad_blocks(P) * ta * tb * 256 * sizeof(float);
+static size_t gemm_wgrad_bytes(long long P, int Ca, int Cb, int bias, int cu_count) {
+    return (size_t)gemm_wgrad_blocks(P, cu_count) * cdiv(Ca, 16) * cdiv(Cb + bias, 16) * 256 * sizeof(float);
 }
-// all tile pairs in one wave when they fit (<= 4 x 6 tiles); false -> the caller falls back to k_conv_wgrad<1,1,1>
-bool launch_gemm_wgrad(const float* A, int lda, int Ca, const float* Bt, int ldb, int Cb, long long P, float* dW, float* dbias,
-                       hipStream_t st, void* workspace, size_t workspace_bytes) {
-    const int bias = dbias != nullptr;
-    const int ta = cdiv(Ca, 16), tb = cdiv(Cb + bias, 16);
-    if (ta > 4 || tb > 6) return false;
-    const long long blocks = gemm_wgrad_blocks(P);
-    float* scratch = (workspace != nullptr && workspace_bytes >= gemm_wgrad_workspace_bytes(P, Ca, Cb, bias)) ? (float*)workspace : nullptr;
-    bool ok;
-    switch (ta) {
-        case 1: ok = launch_gemm_wgrad_ta<1>(tb, (unsigned)blocks, st, A, Bt, lda, ldb, Ca, Cb, bias, P, dW, dbias, scratch); break;
-        case 2: ok = launch_gemm_wgrad_ta<2>(tb, (unsigned)blocks, st, A, Bt, lda, ldb, Ca, Cb, bias, P, dW, dbias, scratch); break;
-        case 3: ok = launch_gemm_wgrad_ta<3>(tb, (unsigned)blocks, st, A, Bt, lda, ldb, Ca, Cb, bias, P, dW, dbias, scratch); break;
-        default: ok = launch_gemm_wgrad_ta<4>(tb, (unsigned)blocks, st, A, Bt, lda, ldb, Ca, Cb, bias, P, dW, dbias, scratch); break;
-    }
-    if (ok && scratch != nullptr) launch_wgrad_reduce(scratch, 1, (int)blocks, ta * tb, tb, Ca, Cb, bias, 1, dW, dbias, st);
-    return ok;
+// k_conv_wgrad: the taps split over SPLIT waves by the leading kernel dimension, PL position lanes per block.  5x5 always splits (by
+// kh, one position lane); 3x3(x3) splits below ENERF_WGRAD_SPLIT_BELOW positions (two lanes); the rest keeps one wave per group, four lanes.
+static int generic_split(int taps, long long npos) {
+    return taps == 25 ? 5 : ((taps == 27 || taps == 9) && npos < (long long)ENERF_WGRAD_SPLIT_BELOW) ? 3 : 1;
+}
+static int generic_pl(int split) { return split == 5 ? 1 : (split == 3 ? 2 : 4); }
+// position chunks (= blocks per channel-tile pair): enough blocks to fill the chip, >= 8 position groups per wave
+static int generic_chunks(long long npos, int pairs, int taps, bool two_stage, int cu_count) {
+    long long want = (long long)cu_count * (two_stage ? 2 : 4) / pairs;
+    if (want < 1) want = 1;
+    const long long maxc = cdivl(cdivl(npos, 4), generic_pl(generic_split(taps, npos)) * 8);
+    return (int)(want < maxc ? want : (maxc < 1 ? 1 : maxc));
+}
+static size_t generic_bytes(long long npos, int Ca, int Cb, int taps, int bias, int cu_count) {
+    const int pairs = cdiv(Ca, 16) * cdiv(Cb + bias, 16);
+    return (size_t)pairs * generic_chunks(npos, pairs, taps, true, cu_count) * taps * 256 * sizeof(float);
+}
+// k_wgrad2d_3x3_c8 / _p16: persistent blocks over the image tiles, one compact row of Ca*Cb*9 sums each
+static bool tile2d_reach(int kd, int kh, int kw, int Ca, int Cb, int bias, long long npos) {
+    const bool c8 = Ca <= 8 && (Cb <= 8 || Cb == 16 || Cb == 32);
+    const bool p16 = ENERF_WGRAD2D_P16 && ((Ca == 16 && (Cb == 16 || Cb == 32)) || (Ca == 32 && Cb == 32));
+    return ENERF_WGRAD2D_TILE && kd == 1 && kh == 3 && kw == 3 && (c8 || p16) && !bias && npos >= 2048;
+}
+static int tile2d_bpc(int Ca, int Cb) {                 // by LDS (21 / 32 / 54 KB per block; p16: 38 / 60 / 77 KB) and registers
+    if (Ca > 8) return Cb == 32 ? 1 : 3;                // (272 / 356 registers with a 32-channel B: one wave per SIMD)
+    return Cb <= 8 ? ENERF_WGRAD2D_BPC : Cb <= 16 ? 3 : 2;
+}
+static int tile2d_blocks(long long ntiles, int Ca, int Cb, int cu_count) {
+    const long long cap = (long long)cu_count * tile2d_bpc(Ca, Cb);
+    return (int)(ntiles < cap ? ntiles : cap);
+}
+static size_t tile2d_bytes(long long ntiles, int Ca, int Cb, int cu_count) {
+    return (size_t)tile2d_blocks(ntiles, Ca, Cb, cu_count) * Ca * Cb * 9 * sizeof(float);
+}
+// k_wgrad3d_c8.  normal: Ca <= 8 gradient channels, Cb = 8 / 16 / 32 input channels (32: two launch columns of 16); swapped: Ca = 16,
+// Cb <= 8 (the fused heads).  One row of a column's share of dW per block.
+static bool tile3d_reach(int kd, int kh, int kw, int Ca, int Cb, int bias, long long npos) {
+    const bool shape = (Ca <= 8 && (Cb == 8 || Cb == 16 || Cb == 32)) || (Ca == 16 && Cb <= 8);
+    return ENERF_WGRAD3D_TILE && kd == 3 && kh == 3 && kw == 3 && shape && !bias && npos >= 32768;
+}
+static int tile3d_cols(int Ca, int Cb) { return (Ca <= 8 && Cb == 32) ? 2 : 1; }
+static int tile3d_blocks(long long ntiles, int cols, int cu_count) {
+    const long long cap = (long long)cu_count * 2 / cols;               // 76 KB of LDS per block: two per CU
+    return (int)(ntiles < cap ? ntiles : (cap < 1 ? 1 : cap));
+}
+static size_t tile3d_bytes(long long ntiles, int Ca, int Cb, int cu_count) {
+    const int cols = tile3d_cols(Ca, Cb);
+    return (size_t)cols * tile3d_blocks(ntiles, cols, cu_count) * Ca * (Cb / cols) * 27 * sizeof(float);
 }
 
-// host side of the group: per member its own block count and scratch slice (what launch_gemm_wgrad would use), then the two launches
+WgradRoute wgrad_route(const WgradShape& p, bool a16, bool b16, size_t workspace_bytes, int cu_count) {
+    WgradRoute r;
+    const long long npos = (long long)p.n * p.Da * p.Ha * p.Wa;
+    const int taps = p.kd * p.kh * p.kw;
+    // stride 1, "same" padding: the output grid is the input grid
+    const bool same = p.stride == 1 && p.Da == p.Db && p.Ha == p.Hb && p.Wa == p.Wb && p.pad_d == p.kd / 2 && p.pad_h == p.kh / 2 &&
+                      p.pad_w == p.kw / 2;
+    const bool a_v4 = a16 && p.lda % 4 == 0, b_v4 = b16 && p.ldb % 4 == 0;       // whole positions can be read with 16-byte loads
+    // The tile kernels have no atomic form: without their workspace, or with a B tile (p16: either tile) that cannot be staged with
+    // 16-byte loads, the layer stays on k_conv_wgrad.  A <= 8-channel tile of A (of B too in the 2-D kernel) can be staged by scalars.
+    if (tile2d_reach(p.kd, p.kh, p.kw, p.Ca, p.Cb, p.bias, npos) && same && p.Da == 1) {
+        const bool p16 = p.Ca > 8;
+        const int tiles_y = cdiv(p16 ? p.Ha : p.Ha + 1, kW2TH), tiles_x = cdiv(p.Wa, kW2TW);      // (c8: from one row above the image)
+        const long long ntiles = (long long)p.n * tiles_y * tiles_x;
+        const bool b4 = (p.Cb == 4 || p.Cb == 8 || p.Cb == 16 || p.Cb == 32) && b_v4;
+        if (workspace_bytes >= tile2d_bytes(ntiles, p.Ca, p.Cb, cu_count) && (p16 ? a_v4 && b_v4 : p.Cb <= 8 || b4)) {
+            r.family = p16 ? kWgrad2dP16 : kWgrad2dC8;
+            if (p16) { r.NA = p.Ca / 16; r.NB = p.Cb / 16; }
+            else { r.A4 = (p.Ca == 4 || p.Ca == 8) && a_v4; r.B4 = b4; r.NCB = p.Cb == 32 ? 4 : (p.Cb == 16 ? 2 : 1); }
+            r.tiles_y = tiles_y; r.tiles_x = tiles_x;
+            r.blocks = r.chunks = tile2d_blocks(ntiles, p.Ca, p.Cb, cu_count);
+            r.scratch_bytes = tile2d_bytes(ntiles, p.Ca, p.Cb, cu_count);
+            return r;
+        }
+    }
+    if (tile3d_reach(p.kd, p.kh, p.kw, p.Ca, p.Cb, p.bias, npos) && same) {
+        const bool swapped = p.Ca > 8;                                // the kernel's A' is the <= 8-channel side, its B' the other
+        const int tiles_y = cdiv(p.Ha + 1, kW2TH), tiles_x = cdiv(p.Wa, kW2TW), Cak = swapped ? p.Cb : p.Ca;
+        const long long ntiles = (long long)p.n * p.Da * tiles_y * tiles_x;
+        if (workspace_bytes >= tile3d_bytes(ntiles, p.Ca, p.Cb, cu_count) && (swapped ? a_v4 : b_v4)) {
+            r.family = kWgrad3dC8;
+            r.swapped = swapped;
+            r.cols = tile3d_cols(p.Ca, p.Cb);
+            r.A4 = (Cak == 4 || Cak == 8) && (swapped ? b_v4 : a_v4);
+            r.NCB = (swapped ? p.Ca : p.Cb) / r.cols == 16 ? 2 : 1;
+            r.tiles_y = tiles_y; r.tiles_x = tiles_x;
+            r.blocks = r.chunks = tile3d_blocks(ntiles, r.cols, cu_count);
+            r.scratch_bytes = tile3d_bytes(ntiles, p.Ca, p.Cb, cu_count);
+            return r;
+        }
+    }
+    // k_gemm_wgrad and k_conv_wgrad: two stages through the workspace, or fp32 atomics when it does not hold their partial tiles
+    r.tiles_a = cdiv(p.Ca, 16);
+    r.tiles_b = cdiv(p.Cb + p.bias, 16);
+    size_t bytes;
+    if (gemm_reach(p.kd, p.kh, p.kw, p.Ca, p.Cb, p.bias, p.linear) && same &&
+        npos * (long long)(p.lda > p.ldb ? p.lda : p.ldb) < (1LL << 30)) {           // (32-bit byte offsets inside the kernel)
+        r.family = kWgradGemm;
+        r.TA = r.tiles_a; r.TB = r.tiles_b;
+        bytes = gemm_wgrad_bytes(npos, p.Ca, p.Cb, p.bias, cu_count);
+        r.blocks = r.chunks = (int)gemm_wgrad_blocks(npos, cu_count);
+    } else if ((p.kd == 3 && p.kh == 3 && p.kw == 3) || (p.kd == 1 && p.kh == p.kw && (p.kh == 3 || p.kh == 5 || p.kh == 1))) {
+        r.family = kWgradGeneric;
+        r.KD = p.kd; r.KH = p.kh; r.KW = p.kw;
+        r.SPLIT = generic_split(taps, npos);
+        r.PL = generic_pl(r.SPLIT);
+        bytes = generic_bytes(npos, p.Ca, p.Cb, taps, p.bias, cu_count);
+        r.chunks = generic_chunks(npos, r.tiles_a * r.tiles_b, taps, workspace_bytes >= bytes, cu_count);
+        r.blocks = r.tiles_a * r.tiles_b * r.chunks;
+    } else {
+        return WgradRoute();
+    }
+    r.atomic = workspace_bytes < bytes;
+    r.scratch_bytes = r.atomic ? 0 : bytes;
+    return r;
+}
+const char* wgrad_route_second_stage(const WgradRoute& r) {
+    if (r.family == kWgradNone || r.atomic) return "";
+    return r.family == kWgradGemm || r.family == kWgradGeneric ? "wgrad_reduce" : "colsum";
+}
+void wgrad_route_name(const WgradRoute& r, char* buf, size_t cap) {
+    auto tf = [](bool v) { return v ? "true" : "false"; };
+    switch (r.family) {
+        case kWgradGemm: snprintf(buf, cap, "gemm_wgrad<%d,%d>", r.TA, r.TB); break;
+        case kWgrad2dC8: snprintf(buf, cap, "wgrad2d_3x3_c8<%s,%s,%d>", tf(r.A4), tf(r.B4), r.NCB); break;
+        case kWgrad2dP16: snprintf(buf, cap, "wgrad2d_3x3_p16<%d,%d>", r.NA, r.NB); break;
+        case kWgrad3dC8: snprintf(buf, cap, "wgrad3d_c8<%s,%d>", tf(r.A4), r.NCB); break;
+        case kWgradGeneric: snprintf(buf, cap, "conv_wgrad<%d,%d,%d,%d,%d>", r.KD, r.KH, r.KW, r.SPLIT, r.PL); break;
+        default: snprintf(buf, cap, "none"); break;
+    }
+}
+// what the C queries can say without the grid: the largest scratch_bytes of a route these arguments can reach.  (A tile kernel's
+// blocks are its tiles up to a cap, and npos positions make at most npos tiles.)
+static size_t conv_wgrad_workspace_bytes(long long npos, int Ca, int Cb, int kd, int kh, int kw, int cu_count) {
+    size_t t = generic_bytes(npos, Ca, Cb, kd * kh * kw, 0, cu_count);
+    auto raise = [&t](size_t v) { t = t > v ? t : v; };
+    if (gemm_reach(kd, kh, kw, Ca, Cb, 0, false)) raise(gemm_wgrad_bytes(npos, Ca, Cb, 0, cu_count));
+    if (tile2d_reach(kd, kh, kw, Ca, Cb, 0, npos)) raise(tile2d_bytes(npos, Ca, Cb, cu_count));
+    if (tile3d_reach(kd, kh, kw, Ca, Cb, 0, npos)) raise(tile3d_bytes(npos, Ca, Cb, cu_count));
+    return t;
+}
+static size_t gemm_wgrad_workspace_bytes(long long P, int Ca, int Cb, int bias, int cu_count) {
+    return gemm_reach(1, 1, 1, Ca, Cb, bias, true) ? gemm_wgrad_bytes(P, Ca, Cb, bias, cu_count) : generic_bytes(P, Ca, Cb, 1, bias, cu_count);
+}
+
+// ---- launchers: the grid and the instantiation are the route's; scratch = the workspace, or nullptr for the atomic commit ----
+static void launch_gemm_wgrad(const WgradShape& p, const WgradRoute& r, const float* A, const float* Bt, float* dW, float* dbias, float* scratch,
+                              hipStream_t st) {
+    const long long P = (long long)p.n * p.Da * p.Ha * p.Wa;
+#define ENERF_GW(TA_, TB_)                                                                                                              \
+    case TA_ * 8 + TB_:                                                                                                                 \
+        ENERF_LAUNCH((k_gemm_wgrad<TA_, TB_>), (unsigned)r.blocks, 256, 0, st, A, Bt, p.lda, p.ldb, p.Ca, p.Cb, p.bias, P, dW, dbias, scratch); \
+        break;
+    switch (r.TA * 8 + r.TB) {
+        ENERF_GW(1, 1) ENERF_GW(1, 2) ENERF_GW(1, 3) ENERF_GW(1, 4) ENERF_GW(1, 5) ENERF_GW(1, 6)
+        ENERF_GW(2, 1) ENERF_GW(2, 2) ENERF_GW(2, 3) ENERF_GW(2, 4) ENERF_GW(2, 5) ENERF_GW(2, 6)
+        ENERF_GW(3, 1) ENERF_GW(3, 2) ENERF_GW(3, 3) ENERF_GW(3, 4) ENERF_GW(3, 5) ENERF_GW(3, 6)
+        ENERF_GW(4, 1) ENERF_GW(4, 2) ENERF_GW(4, 3) ENERF_GW(4, 4) ENERF_GW(4, 5) ENERF_GW(4, 6)
+    }
+#undef ENERF_GW
+    if (scratch != nullptr) launch_wgrad_reduce(scratch, 1, r.chunks, r.TA * r.TB, r.TB, p.Ca, p.Cb, p.bias, 1, dW, dbias, st);
+}
+static void launch_wgrad2d(const WgradShape& p, const WgradRoute& r, const float* A, const float* Bt, float* dW, float* scratch, hipStream_t st) {
+    const int n = p.n, H = p.Ha, W = p.Wa;
+    const unsigned abytes = (unsigned)((long long)n * H * W * p.lda * 4), bbytes = (unsigned)((long long)n * H * W * p.ldb * 4);   // (< 2^32: checked by the C entries)
+#define ENERF_W2P(NA_, NB_) ENERF_LAUNCH((k_wgrad2d_3x3_p16<NA_, NB_>), (unsigned)r.blocks, 256, 0, st, A, Bt, n, H, W, p.lda, p.ldb, r.tiles_y, r.tiles_x, abytes, bbytes, scratch)
+#define ENERF_W2(A4_, B4_, NCB_) ENERF_LAUNCH((k_wgrad2d_3x3_c8<A4_, B4_, NCB_>), (unsigned)r.blocks, 256, 0, st, A, Bt, n, H, W, p.Ca, p.Cb, p.lda, p.ldb, r.tiles_y, r.tiles_x, abytes, bbytes, scratch)
+    if (r.family == kWgrad2dP16) {                         // 16 / 32 channels: the plain tiles
+        if (r.NA == 2) ENERF_W2P(2, 2); else if (r.NB == 2) ENERF_W2P(1, 2); else ENERF_W2P(1, 1);
+    } else if (r.NCB == 4) { if (r.A4) ENERF_W2(true, true, 4); else ENERF_W2(false, true, 4); }
+    else if (r.NCB == 2) { if (r.A4) ENERF_W2(true, true, 2); else ENERF_W2(false, true, 2); }
+    else if (r.A4) { if (r.B4) ENERF_W2(true, true, 1); else ENERF_W2(true, false, 1); }
+    else { if (r.B4) ENERF_W2(false, true, 1); else ENERF_W2(false, false, 1); }
+#undef ENERF_W2
+#undef ENERF_W2P
+    const int n_row = p.Ca * p.Cb * 9;
+    launch_colsum(scratch, r.chunks, n_row, n_row, 0, dW, cdiv(n_row, 64), 1, st);
+}
+static void launch_wgrad3d(const WgradShape& p, const WgradRoute& r, const float* A, const float* Bt, float* dW, float* scratch, hipStream_t st) {
+    const int n = p.n, D = p.Da, H = p.Ha, W = p.Wa;
+    const float* Ak = r.swapped ? Bt : A;                  // the kernel's A' (<= 8 channels) and B' (8 or 16 per column)
+    const float* Bk = r.swapped ? A : Bt;
+    const int Cak = r.swapped ? p.Cb : p.Ca, ldak = r.swapped ? p.ldb : p.lda, ldbk = r.swapped ? p.lda : p.ldb;
+    const int Cbt = r.swapped ? p.Ca : p.Cb, Cbk = Cbt / r.cols;
+    const unsigned abytes = (unsigned)((long long)n * D * H * W * ldak * 4), bbytes = (unsigned)((long long)n * D * H * W * ldbk * 4);
+    const dim3 grid((unsigned)r.blocks, (unsigned)r.cols);
+#define ENERF_W3(A4_, NCB_) ENERF_LAUNCH((k_wgrad3d_c8<A4_, NCB_>), grid, 256, 0, st, Ak, Bk, n, D, H, W, Cak, Cbk, ldak, ldbk, r.tiles_y, r.tiles_x, r.swapped ? 1 : 0, abytes, bbytes, scratch)
+    if (r.NCB == 2) { if (r.A4) ENERF_W3(true, 2); else ENERF_W3(false, 2); }
+    else { if (r.A4) ENERF_W3(true, 1); else ENERF_W3(false, 1); }
+#undef ENERF_W3
+    const int n_row = Cak * Cbk * 27;
+    launch_colsum(scratch, r.chunks, n_row, r.swapped ? n_row : Cbk * 27, Cbt * 27, dW, cdiv(n_row, 64), r.cols, st);
+}
+static void launch_conv_wgrad(const WgradShape& p, const WgradRoute& r, const float* A, const float* Bt, float* dW, float* dbias, float* scratch,
+                              hipStream_t st) {
+    WgradGeom q;
+    q.n = p.n; q.Da = p.Da; q.Ha = p.Ha; q.Wa = p.Wa; q.Ca = p.Ca; q.Db = p.Db; q.Hb = p.Hb; q.Wb = p.Wb; q.Cb = p.Cb;
+    q.stride = p.stride; q.pad_d = p.pad_d; q.pad_h = p.pad_h; q.pad_w = p.pad_w;
+    q.tiles_a = r.tiles_a; q.tiles_b = r.tiles_b; q.chunks = r.chunks;
+    q.lda = p.lda; q.ldb = p.ldb; q.bias = p.bias;
+    q.npos = (long long)p.n * p.Da * p.Ha * p.Wa;
+    q.abytes = (unsigned)(q.npos * q.lda * 4);                       // (< 2^32: checked by the C entries)
+    q.bbytes = (unsigned)((long long)p.n * p.Db * p.Hb * p.Wb * q.ldb * 4);
+#define ENERF_WK(KD_, KH_, KW_, SPLIT_, PL_) \
+    ENERF_LAUNCH((k_conv_wgrad<KD_, KH_, KW_, SPLIT_, PL_>), (unsigned)r.blocks, SPLIT_ * PL_ * 64, 0, st, A, Bt, q, dW, dbias, scratch)
+    if (r.KD == 3) { if (r.SPLIT == 3) ENERF_WK(3, 3, 3, 3, 2); else ENERF_WK(3, 3, 3, 1, 4); }           // wave = (kd, position lane)
+    else if (r.KH == 3) { if (r.SPLIT == 3) ENERF_WK(1, 3, 3, 3, 2); else ENERF_WK(1, 3, 3, 1, 4); }      // wave = (kh, position lane)
+    else if (r.KH == 5) ENERF_WK(1, 5, 5, 5, 1);                                                          // wave = kh
+    else ENERF_WK(1, 1, 1, 1, 4);
+#undef ENERF_WK
+    if (scratch != nullptr)
+        launch_wgrad_reduce(scratch, r.tiles_a * r.tiles_b, r.chunks, r.KD * r.KH * r.KW, r.tiles_b, p.Ca, p.Cb, p.bias, 0, dW, dbias, st);
+}
+// r = wgrad_route(...) of this problem with these operands and at least r.scratch_bytes of workspace.  false for kWgradNone (nothing launched).
+static bool launch_wgrad(const WgradShape& p, const WgradRoute& r, const float* A, const float* Bt, float* dW, float* dbias, void* workspace,
+                         hipStream_t st) {
+    float* scratch = r.atomic ? nullptr : (float*)workspace;
+    switch (r.family) {
+        case kWgradGemm: launch_gemm_wgrad(p, r, A, Bt, dW, dbias, scratch, st); return true;
+        case kWgrad2dC8:
+        case kWgrad2dP16: launch_wgrad2d(p, r, A, Bt, dW, scratch, st); return true;
+        case kWgrad3dC8: launch_wgrad3d(p, r, A, Bt, dW, scratch, st); return true;
+        case kWgradGeneric: launch_conv_wgrad(p, r, A, Bt, dW, dbias, scratch, st); return true;
+        default: return false;
+    }
+}
+
+// host side of the group: per member its own block count and scratch slice (those of its single call's route), then the two launches
 static size_t gemm_group_plan(const enerf_gemm_wgrad_desc_t* u, int n, GemmGroup* G) {
     size_t floats = 0;
     int block0 = 0, rblock0 = 0;
+    const int cu_count = device_cu_count();
     for (int i = 0; i < n; ++i) {
         const int bias = u[i].grad_bias != nullptr, ta = cdiv(u[i].Ca, 16), tb = cdiv(u[i].Cb + bias, 16);
         const bool pre = u[i].partials != nullptr;               // first stage done elsewhere: reduce only, no scratch of ours
-        const int blocks = pre ? u[i].partial_chunks : (int)gemm_wgrad_blocks(u[i].P);
+        const int blocks = pre ? u[i].partial_chunks : (int)gemm_wgrad_blocks(u[i].P, cu_count);
         if (G != nullptr) {
             GemmDesc& d = G->d[i];
             d.A = u[i].a; d.B = u[i].b; d.dW = u[i].grad_w; d.dbias = u[i].grad_bias; d.scratch = nullptr;
@@ -1226,9 +1265,12 @@ int enerf_gemm_wgrad_group(const enerf_gemm_wgrad_desc_t* descs, int n, void* wo
 // scratch for the two-stage (atomic-free, deterministic) commit of the weight gradients; without it the entries fall back to
 // fp32 atomics onto grad_w (correct, several times slower: see k_wgrad_reduce)
 size_t enerf_conv_wgrad_workspace_bytes(long long positions_a, int Ca, int Cb, int kd, int kh, int kw) {
-    return conv_wgrad_workspace_bytes(positions_a, Ca, Cb, kd * kh * kw, 0);
+    return conv_wgrad_workspace_bytes(positions_a, Ca, Cb, kd, kh, kw, device_cu_count());
 }
-size_t enerf_gemm_wgrad_workspace_bytes(long long P, int Ca, int Cb, int with_bias) { return gemm_wgrad_workspace_bytes(P, Ca, Cb, with_bias != 0); }
+size_t enerf_gemm_wgrad_workspace_bytes(long long P, int Ca, int Cb, int with_bias) {
+    return gemm_wgrad_workspace_bytes(P, Ca, Cb, with_bias != 0, device_cu_count());
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int enerf_conv_wgrad(const float* a_cl, const float* b_cl, int n, int Da, int Ha, int Wa, int Ca, int Db, int Hb, int Wb,
                      int Cb, int kd, int kh, int kw, int stride, int pad_d, int pad_h, int pad_w, float* grad_w, void* workspace,
@@ -1239,32 +1281,31 @@ int enerf_conv_wgrad(const float* a_cl, const float* b_cl, int n, int Da, int Ha
     REQUIRE((long long)n * Da * Ha * Wa < (1LL << 31) && (long long)n * Db * Hb * Wb < (1LL << 31), "conv_wgrad: more than 2^31 positions");
     REQUIRE((long long)n * Da * Ha * Wa * Ca < (1LL << 30) && (long long)n * Db * Hb * Wb * Cb < (1LL << 30),
             "conv_wgrad: a tensor of 4 GiB or more (32-bit byte offsets inside the kernel)");
-    const bool two_stage = workspace != nullptr &&
-                           workspace_bytes >= conv_wgrad_workspace_bytes((long long)n * Da * Ha * Wa, Ca, Cb, kd * kh * kw, 0);
-    if (!two_stage) zero_async(grad_w, (size_t)Ca * Cb * kd * kh * kw * sizeof(float), (hipStream_t)stream);
-    if (!launch_conv_wgrad(a_cl, b_cl, n, Da, Ha, Wa, Ca, Db, Hb, Wb, Cb, kd, kh, kw, stride, pad_d, pad_h, pad_w, grad_w,
-                           (hipStream_t)stream, 0, 0, nullptr, workspace, workspace_bytes))
+    const WgradShape p = {n, Da, Ha, Wa, Ca, Db, Hb, Wb, Cb, Ca, Cb, kd, kh, kw, stride, pad_d, pad_h, pad_w, 0, false};
+    const WgradRoute r = wgrad_route(p, aligned16(a_cl), aligned16(b_cl), workspace != nullptr ? workspace_bytes : 0, device_cu_count());
+    if (r.family == kWgradNone)
         return fail(ENERF_EINVAL, "conv_wgrad: kernel %dx%dx%d unsupported (3x3x3, 1x3x3, 1x5x5, 1x1x1)", kd, kh, kw);
+    if (r.atomic) zero_async(grad_w, (size_t)Ca * Cb * kd * kh * kw * sizeof(float), (hipStream_t)stream);
+    launch_wgrad(p, r, a_cl, b_cl, grad_w, nullptr, workspace, (hipStream_t)stream);
     return check_launch("conv_wgrad");
 }
 
 // Plain position-reduction GEMM: grad_w[a][b] = sum_p A[p][a] * B[p][b] — the weight gradient of a Linear layer from its
 // pre-activation gradient A (P rows, Ca used columns of rows lda floats wide) and its input B (P x Cb, rows ldb wide).
 // grad_bias (nullable): the layer's bias gradient sum_p A[p][a], from the same pass (a virtual all-ones column of B).
+// More than 4 x 6 tiles: k_conv_wgrad<1,1,1>, a tile pair per block.
 int enerf_gemm_wgrad(const float* a, int lda, int Ca, const float* b, int ldb, int Cb, long long P, float* grad_w,
                      float* grad_bias, void* workspace, size_t workspace_bytes, enerf_stream_t stream) {
     REQUIRE(a && b && grad_w && Ca > 0 && Cb > 0 && lda >= Ca && ldb >= Cb, "gemm_wgrad: bad arguments");
     REQUIRE(P > 0 && P < (1LL << 31), "gemm_wgrad: P out of range");
     REQUIRE(P * lda < (1LL << 30) && P * ldb < (1LL << 30), "gemm_wgrad: a matrix of 4 GiB or more (32-bit byte offsets inside the kernel)");
-    const bool two_stage = workspace != nullptr && workspace_bytes >= gemm_wgrad_workspace_bytes(P, Ca, Cb, grad_bias != nullptr);
-    if (!two_stage) {
+    const WgradShape p = {1, 1, 1, (int)P, Ca, 1, 1, (int)P, Cb, lda, ldb, 1, 1, 1, 1, 0, 0, 0, grad_bias != nullptr, true};
+    const WgradRoute r = wgrad_route(p, aligned16(a), aligned16(b), workspace != nullptr ? workspace_bytes : 0, device_cu_count());
+    if (r.atomic) {
         zero_async(grad_w, (size_t)Ca * Cb * sizeof(float), (hipStream_t)stream);
         if (grad_bias) zero_async(grad_bias, (size_t)Ca * sizeof(float), (hipStream_t)stream);
-        workspace = nullptr;
     }
-    if (!launch_gemm_wgrad(a, lda, Ca, b, ldb, Cb, P, grad_w, grad_bias, (hipStream_t)stream, workspace, workspace_bytes))
-        launch_conv_wgrad(a, b, 1, 1, 1, (int)P, Ca, 1, 1, (int)P, Cb, 1, 1, 1, 1, 0, 0, 0, grad_w, (hipStream_t)stream, lda, ldb, grad_bias,
-                          workspace, workspace_bytes);
+    launch_wgrad(p, r, a, b, grad_w, grad_bias, workspace, (hipStream_t)stream);       // (a 1x1x1 problem always has a route)
     return check_launch("gemm_wgrad");
 }
 
