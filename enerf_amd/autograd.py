@@ -83,6 +83,80 @@ class CompositeFn(torch.autograd.Function):
         return None, g_raw.view(B, N, Ns, 4), None, None
 
 
+class WindowFeatureVolumeFn(torch.autograd.Function):
+    """FeatureVolumeFn of the voxels inside ``window`` = (x0, y0, ww, wh) of dv's (h, w) grid (homo_warp_composite, utils.py:153-190):
+    feats (B,S,C,Hs,Ws), proj, dv (B,D,h,w) -> cost volume (B,C,D,wh,ww).  dv's gradient is zero outside the window."""
+
+    @staticmethod
+    def forward(ctx, lib: EnerfLib, feats, proj, dv, window):
+        C = feats.shape[2]
+        feat_cl = _c(feats.permute(0, 1, 3, 4, 2))
+        proj, dv = _c(proj.detach()), _c(dv)
+        vol = lib.build_feature_volume_window(feat_cl, proj, dv, C, window)          # (B,D,wh,ww,C)
+        ctx.lib, ctx.window = lib, tuple(int(v) for v in window)
+        ctx.save_for_backward(feat_cl, proj, dv)
+        return vol.permute(0, 4, 1, 2, 3)
+
+    @staticmethod
+    def backward(ctx, g_vol):
+        feat_cl, proj, dv = ctx.saved_tensors
+        g_cl = _c(g_vol.permute(0, 2, 3, 4, 1))
+        g_feat, g_dv = ctx.lib.build_feature_volume_window_bwd(feat_cl, proj, dv, g_cl, ctx.window)
+        return None, g_feat.permute(0, 1, 4, 2, 3), None, g_dv, None
+
+
+class WindowDepthRegressionFn(torch.autograd.Function):
+    """F.pad(prob) + depth_regression (network_composite.py:100-102) without the padded tensor: prob (B,D,wh,ww) of ``window``, dv
+    (B,D,h,w) -> depth, std (B,h,w) over the full grid (outside the window: the moments of a uniform softmax)."""
+
+    @staticmethod
+    def forward(ctx, lib: EnerfLib, prob, dv, depth_inv: bool, window):
+        prob, dv = _c(prob), _c(dv)
+        depth, std = lib.depth_regression_window(prob, dv, depth_inv, window)
+        ctx.lib, ctx.depth_inv, ctx.window = lib, depth_inv, tuple(int(v) for v in window)
+        ctx.save_for_backward(prob, dv)
+        return depth, std
+
+    @staticmethod
+    def backward(ctx, g_depth, g_std):
+        prob, dv = ctx.saved_tensors
+        g_prob, g_dv = ctx.lib.depth_regression_window_bwd(prob, dv, _c(g_depth), _c(g_std), ctx.depth_inv, ctx.window)
+        return None, g_prob, g_dv, None, None
+
+
+class CompositeLayersFn(torch.autograd.Function):
+    """parse_layer + raw2outputs_composite (utils.py:875-942) over L boxed foreground layers and a background.  Call as
+    ``apply(lib, windows, H, W, white_bkgd, bg_raw, bg_z, raw_0, z_0, ..., raw_{L-1}, z_{L-1})`` with raw_l (n_l, Ns, 4) and z_l (n_l, Ns)
+    over the pixels of ``windows[l]`` = (x0, y0, ww, wh) in raster order, bg_raw (H*W, Ns, 4), bg_z (H*W, Ns).  Returns rgb (N, 3),
+    depth (N), weights (N, T), net_output (N, T, 4), z_vals (N, L*Ns).  rgb, depth and weights are differentiable in the raws;
+    net_output and z_vals are returned DETACHED (data movement: the sorted samples and the concatenated depths), and no depth
+    receives a gradient — the reference composites weights * z_vals.detach(), and the sort's permutation has no derivative."""
+
+    @staticmethod
+    def forward(ctx, lib: EnerfLib, windows, H, W, white_bkgd, bg_raw, bg_z, *layers):
+        fg = [(_c(layers[2 * l]), _c(layers[2 * l + 1])) for l in range(len(layers) // 2)]
+        bg = (_c(bg_raw), _c(bg_z))
+        out = lib.composite_layers(fg, windows, bg, H, W, white_bkgd=white_bkgd)
+        ctx.lib, ctx.geom = lib, ([tuple(int(v) for v in w) for w in windows], int(H), int(W), bool(white_bkgd))
+        ctx.save_for_backward(*bg, *[t for pair in fg for t in pair])
+        ctx.mark_non_differentiable(out["net_output"], out["z_vals"])
+        ctx.set_materialize_grads(False)
+        return out["rgb"], out["depth"], out["weights"], out["net_output"], out["z_vals"]
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_weights, _g_net, _g_z):
+        bg_raw, bg_z, *rest = ctx.saved_tensors
+        fg = [(rest[2 * l], rest[2 * l + 1]) for l in range(len(rest) // 2)]
+        windows, H, W, white = ctx.geom
+        opt = lambda g: None if g is None else _c(g)
+        g_fg, g_bg = ctx.lib.composite_layers_bwd(fg, windows, (bg_raw, bg_z), H, W, opt(g_rgb), opt(g_depth), opt(g_weights),
+                                                  white_bkgd=white)
+        grads = [None] * 5 + [g_bg, None]
+        for g in g_fg:
+            grads += [g, None]
+        return tuple(grads)
+
+
 def gather_cameras(batch, render_scale: float, lib):
     """The per-view constants of enerf_gather_*: cam (B,S,16) = K'E33 | K't | source centre | 0 and tcen (B,4), with
     K' = K scaled to the level (utils.py:697-704); products in fp64, stored fp32 (as the inference kernel's table).

@@ -18,11 +18,16 @@ namespace enerf {
 //   f_s = bilinear(feat_s, u, v) (zeros padding)          =>   d feat_s[tap] += w_tap d f_s ;  d u, d v from the tap values
 //   (u, v) = p.xy / max(p.z, 1e-6), p = R [x,y,1] + T / d =>   d d = -(T . d p) / d^2
 // ---------------------------------------------------------------------------------------------------------------------
-template <int CQ>
+// WIN (the composite network's boxed layers, the backward of k_feature_volume_mp<CQ, true>): (h, w) is a WINDOW of the (hf, wf) grid
+// with its corner at (x0, y0).  The thread -> voxel decomposition and gvol (B, D, h, w, C) are the window's; dv is read at, gdv
+// written at and the pixel projected from the voxel's place in the FULL grid (the caller zeroes gdv: outside the window it stays 0).
+// A voxel's gdv depends on no neighbour: inside the window it holds the bits the full launch gives it on a zero-padded gvol.
+template <int CQ, bool WIN = false>
 __global__ __launch_bounds__(256) void k_feature_volume_bwd(const float* __restrict__ feat, const float* __restrict__ proj,
                                                             const float* __restrict__ dv, const float* __restrict__ gvol,
                                                             int B, int S, int Hs, int Ws, int D, int h, int w,
-                                                            float* __restrict__ gfeat, float* __restrict__ gdv) {
+                                                            float* __restrict__ gfeat, float* __restrict__ gdv, int x0w, int y0w,
+                                                            int hf, int wf) {
     constexpr int C = CQ * 4;
     const long long nvox = (long long)B * D * h * w;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -32,8 +37,10 @@ __global__ __launch_bounds__(256) void k_feature_volume_bwd(const float* __restr
     const long long vox = live ? vraw : nvox - 1;
     const int x = (int)(vox % w), y = (int)((vox / w) % h);
     const int b = (int)(vox / ((long long)D * h * w));
-    const float depth = dv[vox];
-    const float fx = (float)x, fy = (float)y;
+    long long fvox = vox;                               // the voxel in dv / gdv
+    if constexpr (WIN) fvox = ((vox / ((long long)h * w)) * hf + (y0w + y)) * wf + (x0w + x);        // (vox / (h w) = b * D + d)
+    const float depth = dv[fvox];
+    const float fx = (float)(WIN ? x0w + x : x), fy = (float)(WIN ? y0w + y : y);
     const float4 g = *reinterpret_cast<const float4*>(gvol + vox * C + cq * 4);
     const long long img = (long long)Hs * Ws * C;
     // pass 1: mean over views of the warped features
@@ -154,17 +161,28 @@ __global__ __launch_bounds__(256) void k_feature_volume_bwd(const float* __restr
     }
     // sum over the CQ channel lanes of the voxel
     for (int m = CQ >> 1; m >= 1; m >>= 1) gd += __shfl_xor(gd, m);
-    if (live && cq == 0) gdv[vox] = gd;
+    if (live && cq == 0) gdv[fvox] = gd;
 }
 bool launch_feature_volume_bwd(const float* feat, const float* proj, const float* dv, const float* gvol, int B, int S, int C,
                                int Hs, int Ws, int D, int h, int w, float* gfeat, float* gdv, hipStream_t st) {
     const long long threads = (long long)B * D * h * w * (C / 4);
     const unsigned grid = (unsigned)cdivl(threads, 256);
     switch (C) {
-        case 32: ENERF_LAUNCH(k_feature_volume_bwd<8>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv); return true;
-        case 16: ENERF_LAUNCH(k_feature_volume_bwd<4>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv); return true;
-        case 8: ENERF_LAUNCH(k_feature_volume_bwd<2>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv); return true;
+        case 32: ENERF_LAUNCH(k_feature_volume_bwd<8>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv, 0, 0, h, w); return true;
+        case 16: ENERF_LAUNCH(k_feature_volume_bwd<4>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv, 0, 0, h, w); return true;
+        case 8: ENERF_LAUNCH(k_feature_volume_bwd<2>, grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, h, w, gfeat, gdv, 0, 0, h, w); return true;
         default: return false;
+    }
+}
+// The window (x0, y0, ww, wh) of the (h, w) grid: gvol (B, D, wh, ww, C); gdv (B, D, h, w), zeroed by the caller.  C in {16, 32}.
+void launch_feature_volume_window_bwd(const float* feat, const float* proj, const float* dv, const float* gvol, int B, int S, int C,
+                                      int Hs, int Ws, int D, int h, int w, int x0, int y0, int ww, int wh, float* gfeat, float* gdv,
+                                      hipStream_t st) {
+    const unsigned grid = (unsigned)cdivl((long long)B * D * wh * ww * (C / 4), 256);
+    switch (C) {
+        case 32: ENERF_LAUNCH((k_feature_volume_bwd<8, true>), grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, wh, ww, gfeat, gdv, x0, y0, h, w); break;
+        case 16: ENERF_LAUNCH((k_feature_volume_bwd<4, true>), grid, 256, 0, st, feat, proj, dv, gvol, B, S, Hs, Ws, D, wh, ww, gfeat, gdv, x0, y0, h, w); break;
+        default: break;   // validated by the C-ABI layer
     }
 }
 
@@ -176,11 +194,15 @@ bool launch_feature_volume_bwd(const float* feat, const float* proj, const float
 // One thread per pixel walked the D <= 64 planes six times with dependent loads and an expf per visit, on 20 blocks for level 0's
 // 64 x 80 pixels: 71 us per launch, two launches per training step.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int MK>
+// WIN (the backward of composite_layers.h k_depth_regression_window): prob and g_prob (B, D, wh, ww) exist only inside the window
+// at (x0, y0); a pixel outside runs the same arithmetic on zero logits (a uniform softmax) and writes g_dv alone — the bits
+// of the plain kernel on the zero-padded prob, whose g_prob outside the window nobody reads.
+template <int MK, bool WIN = false>
 __global__ __launch_bounds__(256) void k_depth_regression_bwd(const float* __restrict__ prob, const float* __restrict__ dv,
                                                               const float* __restrict__ g_depth, const float* __restrict__ g_std,
                                                               int B, int D, int h, int w, int depth_inv,
-                                                              float* __restrict__ g_prob, float* __restrict__ g_dv) {
+                                                              float* __restrict__ g_prob, float* __restrict__ g_dv, int x0, int y0,
+                                                              int ww, int wh) {
     const int lane = threadIdx.x & 63, sl = lane >> 4;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long hw = (long long)h * w;
@@ -188,7 +210,15 @@ __global__ __launch_bounds__(256) void k_depth_regression_bwd(const float* __res
     const bool ok = i < (long long)B * hw;
     const long long ii = ok ? i : 0;                    // dead lanes shadow pixel 0 (they take part in the lane swaps)
     const long long b = ii / hw, p = ii - b * hw;
-    const float* pr = prob + b * D * hw + p;
+    long long hwp = hw, pw = p;                         // prob's plane stride and the pixel's place in a plane of it
+    bool inside = true;
+    if constexpr (WIN) {
+        const int y = (int)(p / w), xx = (int)(p - (long long)y * w);
+        inside = xx >= x0 && xx < x0 + ww && y >= y0 && y < y0 + wh;
+        hwp = (long long)wh * ww;
+        pw = inside ? (long long)(y - y0) * ww + (xx - x0) : 0;
+    }
+    const float* pr = prob + b * D * hwp + pw;
     const float* dp = dv + b * D * hw + p;
     float e[MK], v[MK], d[MK];
     float m = -INFINITY;
@@ -197,7 +227,7 @@ __global__ __launch_bounds__(256) void k_depth_regression_bwd(const float* __res
         const int k = sl + 4 * kk;
         const bool in = k < D;
         const long long o = (long long)(in ? k : 0) * hw;
-        const float x = pr[o];
+        const float x = inside ? pr[(long long)(in ? k : 0) * hwp] : 0.f;
         d[kk] = dp[o];
         e[kk] = in ? x : -INFINITY;
         v[kk] = depth_inv ? 1.f / clamp_min(d[kk], 1e-6f) : d[kk];
@@ -231,7 +261,7 @@ __global__ __launch_bounds__(256) void k_depth_regression_bwd(const float* __res
         if (k >= D) continue;
         const float c = v[kk] - mu, pk = e[kk];
         const float gp = gmu * v[kk] + gvar * c * c;
-        g_prob[b * D * hw + k * hw + p] = pk * (gp - dot);
+        if (inside) g_prob[b * D * hwp + k * hwp + pw] = pk * (gp - dot);
         const float gvk = gmu * pk + gvar * 2.f * pk * c;
         g_dv[b * D * hw + k * hw + p] = depth_inv ? (d[kk] >= 1e-6f ? -gvk / (d[kk] * d[kk]) : 0.f) : gvk;
     }
@@ -284,12 +314,24 @@ void launch_depth_regression_bwd(const float* prob, const float* dv, const float
                                  int h, int w, int depth_inv, float* g_prob, float* g_dv, hipStream_t st) {
     const unsigned grid4 = (unsigned)cdivl((long long)B * h * w, 64);               // 16 pixels per wave, 4 waves per block
     if (D <= 16)
-        ENERF_LAUNCH(k_depth_regression_bwd<4>, grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv);
+        ENERF_LAUNCH(k_depth_regression_bwd<4>, grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv, 0, 0, w, h);
     else if (D <= 64)
-        ENERF_LAUNCH(k_depth_regression_bwd<16>, grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv);
+        ENERF_LAUNCH(k_depth_regression_bwd<16>, grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv, 0, 0, w, h);
     else
         ENERF_LAUNCH_SIMPLE(k_depth_regression_bwd_serial, (unsigned)cdivl((long long)B * h * w, 256), 256, 0, st, prob, dv, g_depth, g_std,
                             B, D, h, w, depth_inv, g_prob, g_dv);
+}
+// g_prob (B, D, wh, ww) of the window, g_dv (B, D, h, w); D <= 64 (the C-ABI layer checks): launch_depth_regression_bwd's branch for D
+void launch_depth_regression_window_bwd(const float* prob, const float* dv, const float* g_depth, const float* g_std, int B, int D,
+                                        int h, int w, int x0, int y0, int ww, int wh, int depth_inv, float* g_prob, float* g_dv,
+                                        hipStream_t st) {
+    const unsigned grid4 = (unsigned)cdivl((long long)B * h * w, 64);
+    if (D <= 16)
+        ENERF_LAUNCH((k_depth_regression_bwd<4, true>), grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv,
+                     x0, y0, ww, wh);
+    else
+        ENERF_LAUNCH((k_depth_regression_bwd<16, true>), grid4, 256, 0, st, prob, dv, g_depth, g_std, B, D, h, w, depth_inv, g_prob, g_dv,
+                     x0, y0, ww, wh);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -463,6 +463,54 @@ int enerf_depth_regression_window(const float* prob, const float* depth_values, 
     launch_depth_regression_window(prob, depth_values, B, D, h, w, x0, y0, ww, wh, depth_inv, depth, std, (hipStream_t)stream);
     return check_launch("depth_regression_window");
 }
+int enerf_build_feature_volume_window_bwd(const float* feat, const float* proj, const float* depth_values, const float* grad_vol, int B,
+                                          int S, int C, int Hs, int Ws, int D, int h, int w, int x0, int y0, int ww, int wh,
+                                          float* grad_feat, float* grad_depth_values, enerf_stream_t stream) {
+    REQUIRE(feat && proj && depth_values && grad_vol && grad_feat && grad_depth_values, "build_feature_volume_window_bwd: null pointer");
+    REQUIRE(C == 16 || C == 32, "build_feature_volume_window_bwd: C=%d unsupported (16/32)", C);
+    REQUIRE(B > 0 && S > 0 && Hs > 1 && Ws > 1 && D > 0, "build_feature_volume_window_bwd: bad shape");
+    if (int rc = check_window("build_feature_volume_window_bwd", h, w, x0, y0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "build_feature_volume_window_bwd: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww,
+            D);
+    REQUIRE((long long)B * S * Hs * Ws * C < (1LL << 31), "build_feature_volume_window_bwd: feature maps of %lld floats (limit 2^31)",
+            (long long)B * S * Hs * Ws * C);
+    REQUIRE((long long)B * D * h * w * (C / 4) < (1LL << 31), "build_feature_volume_window_bwd: grid too large for 32-bit voxel indices");
+    zero_async2(grad_feat, (size_t)B * S * Hs * Ws * C * sizeof(float), grad_depth_values, (size_t)B * D * h * w * sizeof(float),
+                (hipStream_t)stream);
+    launch_feature_volume_window_bwd(feat, proj, depth_values, grad_vol, B, S, C, Hs, Ws, D, h, w, x0, y0, ww, wh, grad_feat,
+                                     grad_depth_values, (hipStream_t)stream);
+    return check_launch("build_feature_volume_window_bwd");
+}
+int enerf_depth_regression_window_bwd(const float* prob, const float* depth_values, const float* grad_depth, const float* grad_std,
+                                      int B, int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv, float* grad_prob,
+                                      float* grad_depth_values, enerf_stream_t stream) {
+    REQUIRE(prob && depth_values && grad_depth && grad_std && grad_prob && grad_depth_values, "depth_regression_window_bwd: null pointer");
+    REQUIRE(B > 0 && D > 0 && D <= 64, "depth_regression_window_bwd: B=%d, D=%d unsupported (D in 1..64)", B, D);
+    if (int rc = check_window("depth_regression_window_bwd", h, w, x0, y0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "depth_regression_window_bwd: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww, D);
+    REQUIRE((long long)B * D * h * w < (1LL << 31), "depth_regression_window_bwd: grid too large");
+    launch_depth_regression_window_bwd(prob, depth_values, grad_depth, grad_std, B, D, h, w, x0, y0, ww, wh, depth_inv, grad_prob,
+                                       grad_depth_values, (hipStream_t)stream);
+    return check_launch("depth_regression_window_bwd");
+}
+int enerf_composite_layers_bwd(const enerf_composite_layers_bwd_t* g, enerf_stream_t stream) {
+    REQUIRE(g, "composite_layers_bwd: null args");
+    const enerf_composite_layers_t* a = &g->fwd;
+    REQUIRE(a->L >= 1 && a->L <= ENERF_MAX_FG_LAYERS && a->Ns >= 1 && a->L * a->Ns <= 16,
+            "composite_layers_bwd: L=%d foreground layers x %d samples unsupported (L in 1..%d, L*n_samples <= 16)", a->L, a->Ns,
+            ENERF_MAX_FG_LAYERS);
+    REQUIRE(a->H > 0 && a->W > 0 && (long long)a->H * a->W * (a->L + 1) * a->Ns * 4 < (1LL << 31), "composite_layers_bwd: bad image size");
+    REQUIRE(a->bg_raw && a->bg_z && g->grad_bg_raw, "composite_layers_bwd: null pointer");       // grad_rgb / _depth / _weights: NULL = zeros
+    REQUIRE(((uintptr_t)a->bg_raw | (uintptr_t)g->grad_bg_raw) % 16 == 0, "composite_layers_bwd: bg_raw / grad_bg_raw must be 16-byte aligned");
+    for (int l = 0; l < a->L; ++l) {
+        REQUIRE(a->fg_raw[l] && a->fg_z[l] && g->grad_fg_raw[l], "composite_layers_bwd: layer %d: null pointer", l);
+        REQUIRE(((uintptr_t)a->fg_raw[l] | (uintptr_t)g->grad_fg_raw[l]) % 16 == 0,
+                "composite_layers_bwd: layer %d: fg_raw / grad_fg_raw must be 16-byte aligned", l);
+        if (int rc = check_window("composite_layers_bwd", a->H, a->W, a->win[l][0], a->win[l][1], a->win[l][2], a->win[l][3])) return rc;
+    }
+    launch_composite_layers_bwd(*g, (hipStream_t)stream);
+    return check_launch("composite_layers_bwd");
+}
 int enerf_window_ray_index(int x0, int y0, int ww, int wh, int Hr, int Wr, int* index, int* count, enerf_stream_t stream) {
     REQUIRE(index && count, "window_ray_index: null pointer");
     if (int rc = check_window("window_ray_index", Hr, Wr, x0, y0, ww, wh)) return rc;

@@ -339,6 +339,14 @@ void launch_window_ray_index(int x0, int y0, int ww, int wh, int Wr, int* index,
 void launch_composite_layers(const enerf_composite_layers_t& a, hipStream_t st, const int* invalid = nullptr);
 // enerf_composite_layers with the cached frame's device flag (nonzero: every output NaN; nullptr: the C entry itself)
 int composite_layers_run(const enerf_composite_layers_t* a, const int* invalid, hipStream_t st);
+// the backwards the composite network's training step adds (backward.hip: the windowed template values; composite_layers.h)
+void launch_feature_volume_window_bwd(const float* feat, const float* proj, const float* dv, const float* gvol, int B, int S, int C,
+                                      int Hs, int Ws, int D, int h, int w, int x0, int y0, int ww, int wh, float* gfeat, float* gdv,
+                                      hipStream_t st);
+void launch_depth_regression_window_bwd(const float* prob, const float* dv, const float* g_depth, const float* g_std, int B, int D,
+                                        int h, int w, int x0, int y0, int ww, int wh, int depth_inv, float* g_prob, float* g_dv,
+                                        hipStream_t st);
+void launch_composite_layers_bwd(const enerf_composite_layers_bwd_t& g, hipStream_t st);
 // the composite frame's camera-only preparation (prep_job.h CompositePrep, geometry.hip k_composite_prep): composite_prep_job checks
 // the C arguments and lays the job out (ENERF_EINVAL + message, nothing launched), launch_composite_prep runs it
 struct CompositePrep;

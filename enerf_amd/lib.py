@@ -111,6 +111,12 @@ class CompositeLayersArgs(C.Structure):
                 + [(n, _f) for n in ("rgb", "depth", "weights", "net_output", "z_vals")])
 
 
+class CompositeLayersBwdArgs(C.Structure):
+    """``enerf_composite_layers_bwd_t``."""
+    _fields_ = [("fwd", CompositeLayersArgs), ("grad_rgb", _f), ("grad_depth", _f), ("grad_weights", _f),
+                ("grad_fg_raw", C.c_void_p * MAX_FG_LAYERS), ("grad_bg_raw", _f)]
+
+
 MAX_LEVELS = 3
 STAGE_COUNT = 2 + 6 * MAX_LEVELS
 STAGE_NAMES = ["begin", "feature_net"] + [f"{n}_{i}" for i in range(MAX_LEVELS)
@@ -346,6 +352,9 @@ _SIGNATURES = {
     "enerf_window_ray_index": (_i, [_i] * 6 + [C.c_void_p, C.c_void_p, _f]),
     "enerf_render_rays_raw": (_i, [C.POINTER(RenderRawArgs), _f]),
     "enerf_composite_layers": (_i, [C.POINTER(CompositeLayersArgs), _f]),
+    "enerf_build_feature_volume_window_bwd": (_i, [_f, _f, _f, _f] + [_i] * 12 + [_f, _f, _f]),
+    "enerf_depth_regression_window_bwd": (_i, [_f, _f, _f, _f] + [_i] * 9 + [_f, _f, _f]),
+    "enerf_composite_layers_bwd": (_i, [C.POINTER(CompositeLayersBwdArgs), _f]),
     "enerf_composite_prep": (_i, [C.POINTER(CompositePrepArgs), _f]),
     "enerf_forward_composite_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs)]),
     "enerf_forward_composite": (_i, [C.POINTER(CompositeFrameArgs), _f]),
@@ -885,6 +894,65 @@ class EnerfLib:
                                                         int(depth_inv), _ptr(gp), _ptr(gdv), self.stream_of(prob)),
                     "depth_regression_bwd")
         return gp, gdv
+
+    # -- backward kernels of the composite network (windows as in the forward methods) --
+    def build_feature_volume_window_bwd(self, feat_cl, proj, dv, grad_vol, window):
+        """Backward of :meth:`build_feature_volume_window`: ``grad_vol`` (B, D, wh, ww, C) -> (grad_feat like ``feat_cl``, grad_dv
+        like ``dv``; exactly 0 outside the window)."""
+        B, S, Hs, Ws, Cc = feat_cl.shape
+        _, D, h, w = dv.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        if tuple(grad_vol.shape) != (B, D, wh, ww, Cc) or not grad_vol.is_contiguous():
+            raise EnerfError(f"build_feature_volume_window_bwd: grad_vol {tuple(grad_vol.shape)} is not a contiguous {(B, D, wh, ww, Cc)}")
+        gfeat, gdv = torch.empty_like(feat_cl), torch.empty_like(dv)
+        self._check(self.dll.enerf_build_feature_volume_window_bwd(_ptr(feat_cl), _ptr(proj), _ptr(dv), _ptr(grad_vol), B, S, Cc, Hs, Ws,
+                                                                   D, h, w, x0, y0, ww, wh, _ptr(gfeat), _ptr(gdv), self.stream_of(dv)),
+                    "build_feature_volume_window_bwd")
+        return gfeat, gdv
+
+    def depth_regression_window_bwd(self, prob, dv, g_depth, g_std, depth_inv, window):
+        """Backward of :meth:`depth_regression_window`: ``g_depth`` / ``g_std`` (B, h, w) over the full image -> (grad_prob like
+        ``prob``, grad_dv like ``dv``)."""
+        B, D, h, w = dv.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        if tuple(prob.shape) != (B, D, wh, ww) or tuple(g_depth.shape) != (B, h, w) or tuple(g_std.shape) != (B, h, w):
+            raise EnerfError(f"depth_regression_window_bwd: prob {tuple(prob.shape)} is not {(B, D, wh, ww)}, or g_depth / g_std "
+                             f"{tuple(g_depth.shape)} / {tuple(g_std.shape)} not {(B, h, w)}")
+        gp, gdv = torch.empty_like(prob), torch.empty_like(dv)
+        self._check(self.dll.enerf_depth_regression_window_bwd(_ptr(prob), _ptr(dv), _ptr(g_depth), _ptr(g_std), B, D, h, w, x0, y0, ww,
+                                                               wh, int(depth_inv), _ptr(gp), _ptr(gdv), self.stream_of(dv)),
+                    "depth_regression_window_bwd")
+        return gp, gdv
+
+    def composite_layers_bwd(self, fg, windows, bg, H, W, g_rgb, g_depth, g_weights, white_bkgd=False, out=None):
+        """Backward of :meth:`composite_layers` (same ``fg``, ``windows``, ``bg``): upstream ``g_rgb`` (N, 3), ``g_depth`` (N),
+        ``g_weights`` (N, T), each optional (None = zeros).  Returns ``([grad_raw per layer], grad_bg_raw)`` shaped like the raw
+        inputs; the depths receive no gradient.  ``out`` = the same pair, preallocated."""
+        L, (bg_raw, bg_z) = len(fg), bg
+        Ns, N = int(bg_z.shape[-1]), H * W
+        if L > MAX_FG_LAYERS or len(windows) != L:
+            raise EnerfError(f"composite_layers_bwd: {L} foreground layers, {len(windows)} windows (at most {MAX_FG_LAYERS}, one window each)")
+        if bg_raw.numel() != N * Ns * 4 or bg_z.numel() != N * Ns:
+            raise EnerfError("composite_layers_bwd: the background covers the whole (H, W) image")
+        T = (L + 1) * Ns
+        for name, t, n in (("g_rgb", g_rgb, N * 3), ("g_depth", g_depth, N), ("g_weights", g_weights, N * T)):
+            if t is not None and (t.numel() != n or not t.is_contiguous()):
+                raise EnerfError(f"composite_layers_bwd: {name} must be contiguous with {n} elements")
+        g_fg, g_bg = out if out is not None else ([torch.empty_like(raw) for raw, _ in fg], torch.empty_like(bg_raw))
+        a = CompositeLayersBwdArgs()
+        a.fwd.L, a.fwd.Ns, a.fwd.H, a.fwd.W, a.fwd.white_bkgd = L, Ns, int(H), int(W), int(bool(white_bkgd))
+        for l, ((raw, z), win) in enumerate(zip(fg, windows)):
+            x0, y0, ww, wh = (int(v) for v in win)
+            if raw.numel() != max(ww * wh, 0) * Ns * 4 or z.numel() != max(ww * wh, 0) * Ns or g_fg[l].numel() != raw.numel():
+                raise EnerfError(f"composite_layers_bwd: layer {l}: buffers do not hold the window's {ww}x{wh} pixels x {Ns} samples")
+            a.fwd.fg_raw[l], a.fwd.fg_z[l], a.grad_fg_raw[l] = _ptr(raw), _ptr(z), _ptr(g_fg[l])
+            a.fwd.win[l][0], a.fwd.win[l][1], a.fwd.win[l][2], a.fwd.win[l][3] = x0, y0, ww, wh
+        if g_bg.numel() != bg_raw.numel():
+            raise EnerfError("composite_layers_bwd: out's background gradient must be shaped like bg_raw")
+        a.fwd.bg_raw, a.fwd.bg_z, a.grad_bg_raw = _ptr(bg_raw), _ptr(bg_z), _ptr(g_bg)
+        a.grad_rgb, a.grad_depth, a.grad_weights = _ptr(g_rgb), _ptr(g_depth), _ptr(g_weights)
+        self._check(self.dll.enerf_composite_layers_bwd(C.byref(a), self.stream_of(bg_z)), "composite_layers_bwd")
+        return g_fg, g_bg
 
     # training-mode 3-D conv layers / BatchNorm pieces (train.hip); kind: 0 stride 1, 1 stride 2, 2 transposed stride 2
     def conv3d_layer_pack(self, w, cin, cout, kind):

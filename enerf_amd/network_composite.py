@@ -22,7 +22,12 @@ A viewer that draws many target cameras from one rig of V source views per time 
 batch)`` per camera — ``enerf_forward_composite_cached``, the same frame with both nets' maps, the texels and the source cameras
 gathered by a device-resident view index, bit for bit ``forward`` on those views.
 
-Restrictions, all stated in DESIGN.md §8: inference only (``forward`` raises in training mode); ``B == 1`` (the reference reads
+Training is opt-in: ``Network(..., trainable=True)`` in ``.train()`` mode runs the differentiable path of
+``train_path_composite.py`` (every stage on the library in both directions; ``enerf_amd.loss.EnerfLoss`` takes its output dict), and
+the packed weight images — and any source cache — are rebuilt after it.  Without the argument ``forward`` raises in training mode, as
+``forward_cached`` and ``cache_sources`` do on every network.
+
+Restrictions, all stated in DESIGN.md §8: ``B == 1`` (the reference reads
 ``batch['bbox'][0]`` for every batch element); ``feature_backend="hip"``; no ``SequencePlayer`` or multi-GPU driver; the cached
 frame has no staged form (``forward_cached`` with a ``stage_hook`` raises); at most four foreground layers with
 ``num_fg_layers * num_samples <= 16`` per level.
@@ -101,8 +106,9 @@ class Network(nn.Module):
     """ENeRF-Outdoor's layered renderer with the reference's call surface (network_composite.py:11-146)."""
 
     def __init__(self, cfg: Optional[EnerfConfig] = None, num_fg_layers: int = 1, lib: Optional[EnerfLib] = None,
-                 feature_backend: str = "hip", driver: str = "call"):
+                 feature_backend: str = "hip", driver: str = "call", trainable: bool = False):
         super().__init__()
+        self.trainable = bool(trainable)               # opt-in: forward() in .train() mode runs train_path_composite.py
         if feature_backend != "hip":
             raise ValueError("network_composite: feature_backend must be 'hip'")
         if driver not in ("call", "staged"):
@@ -238,7 +244,12 @@ class Network(nn.Module):
         cameras, ``bbox`` (1,L,4) = (x, y, w, h) per foreground layer in pixels of the input image, ``near_far`` (1,L+1,2) with
         the background's range last, and optionally ``rays_{i}`` (1,Hr*Wr,8), the full raster of each rendered level."""
         if self.training:
-            raise RuntimeError("network_composite: inference only — forward() has no training path; call net.eval()")
+            if not getattr(self, "trainable", False):
+                raise RuntimeError("network_composite: inference only — forward() has no training path unless the network was built "
+                                   "with trainable=True; call net.eval()")
+            from .train_path_composite import forward_train_composite
+            self.invalidate_packed()                   # the optimizer is about to change what the packed images (and a source cache) hold
+            return forward_train_composite(self, batch)
         cas, lib, L = self.cfg.cas, self.lib, self.num_fg_layers
         src = batch["src_inps"]
         B, S, _, H, W = src.shape

@@ -867,6 +867,35 @@ typedef struct {
 } enerf_composite_layers_t;
 int enerf_composite_layers(const enerf_composite_layers_t* args, enerf_stream_t stream);
 
+/* ---- backward kernels of the composite network's training step (ABI v11 grew by these three entries; new symbols only, the
+ * version number is unchanged).  Each refuses with ENERF_EINVAL, before any launch, what its forward entry refuses.
+ *   enerf_build_feature_volume_window_bwd   backward of enerf_build_feature_volume_window: grad_vol (B,D,wh,ww,C) of the window,
+ *       depth_values (B,D,h,w) of the full grid -> grad_feat (B,S,Hs,Ws,C), zeroed here and scatter-added (fp32 atomics: the order
+ *       of the sums is arbitrary), and grad_depth_values (B,D,h,w): inside the window the bits enerf_build_feature_volume_bwd
+ *       gives on the full grid with grad_vol zero-padded, exactly 0 outside.  C in {16, 32}; wh, ww, D divisible by 4.
+ *   enerf_depth_regression_window_bwd       backward of enerf_depth_regression_window: prob (B,D,wh,ww) of the window, grad_depth /
+ *       grad_std (B,h,w) over the FULL image (they are not zero outside the window: an align-corners upsampling of depth / std
+ *       reaches past its edge) -> grad_prob (B,D,wh,ww) and grad_depth_values (B,D,h,w), the bits of enerf_depth_regression_bwd on
+ *       the zero-padded prob (outside the window the softmax is uniform), which is never built.  D <= 64, as the forward.
+ *   enerf_composite_layers_bwd              backward of enerf_composite_layers, one thread per pixel, no atomics (bit-identical from
+ *       call to call).  fwd: the forward's inputs (its five output pointers are ignored).  grad_rgb (N,3), grad_depth (N),
+ *       grad_weights (N,T): each may be NULL = zeros.  grad_fg_raw[l] (win[l][2]*win[l][3], n_samples, 4) and grad_bg_raw
+ *       (N, n_samples, 4): every row is written; 16-byte aligned.  No depth receives a gradient: the reference composites
+ *       weights * z_vals.detach(), and the sort's permutation is not differentiable. */
+int enerf_build_feature_volume_window_bwd(const float* feat, const float* proj, const float* depth_values, const float* grad_vol, int B,
+                                          int S, int C, int Hs, int Ws, int D, int h, int w, int x0, int y0, int ww, int wh,
+                                          float* grad_feat, float* grad_depth_values, enerf_stream_t stream);
+int enerf_depth_regression_window_bwd(const float* prob, const float* depth_values, const float* grad_depth, const float* grad_std,
+                                      int B, int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv, float* grad_prob,
+                                      float* grad_depth_values, enerf_stream_t stream);
+typedef struct {
+    enerf_composite_layers_t fwd;
+    const float *grad_rgb, *grad_depth, *grad_weights;
+    float* grad_fg_raw[ENERF_MAX_FG_LAYERS];
+    float* grad_bg_raw;
+} enerf_composite_layers_bwd_t;
+int enerf_composite_layers_bwd(const enerf_composite_layers_bwd_t* args, enerf_stream_t stream);
+
 /* ---- the composite network in one call (ABI v11 grew by these three entries; new symbols only, the version number is unchanged) ----
  * B == 1 throughout.  Cascade c = 0 .. L-1 is foreground layer c, cascade L the background ("background last").
  *   enerf_composite_prep    everything of a composite frame that depends on the cameras, near_far and the boxes alone, in ONE launch:
