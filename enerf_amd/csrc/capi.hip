@@ -427,7 +427,7 @@ int composite_prep_job(const enerf_composite_prep_t* a, CompositePrep* job) {
             REQUIRE(a->index[i][l] && a->count[i][l], "composite_prep: index[%d][%d] / count[%d][%d] is null", i, l, i, l);
             if (int rc = check_window("composite_prep", a->Hr[i], a->Wr[i], wn[0], wn[1], wn[2], wn[3])) return rc;
             const int blocks = composite_prep_job_blocks((long long)wn[2] * wn[3], 256);
-            J.win[J.n_win++] = CompositePrep::Window{wn[0], wn[1], wn[2], wn[3], a->Wr[i], nb, blocks, a->index[i][l], a->count[i][l]};
+            J.win[J.n_win++] = CompositePrep::Window{wn[0], wn[1], wn[2], wn[3], a->Wr[i], nb, blocks, a->index[i][l], a->count[i][l], i, l};
             nb += blocks;
         }
     }
@@ -549,6 +549,10 @@ int enerf_composite_layers(const enerf_composite_layers_t* a, enerf_stream_t str
 }  // extern "C"
 namespace enerf {
 int composite_layers_run(const enerf_composite_layers_t* a, const int* invalid, hipStream_t stream) {
+    return composite_layers_run_at(a, invalid, nullptr, stream);
+}
+// win_xy != nullptr: the corners a.win[l][0..1] are ignored (checked as 0) and read from the device
+int composite_layers_run_at(const enerf_composite_layers_t* a, const int* invalid, const int* win_xy, hipStream_t stream) {
     REQUIRE(a, "composite_layers: null args");
     REQUIRE(a->L >= 1 && a->L <= ENERF_MAX_FG_LAYERS && a->Ns >= 1 && a->L * a->Ns <= 16,
             "composite_layers: L=%d foreground layers x %d samples unsupported (L in 1..%d, L*n_samples <= 16)", a->L, a->Ns,
@@ -559,9 +563,12 @@ int composite_layers_run(const enerf_composite_layers_t* a, const int* invalid, 
     for (int l = 0; l < a->L; ++l) {
         REQUIRE(a->fg_raw[l] && a->fg_z[l], "composite_layers: layer %d: null pointer", l);
         REQUIRE((uintptr_t)a->fg_raw[l] % 16 == 0, "composite_layers: layer %d: fg_raw must be 16-byte aligned", l);
-        if (int rc = check_window("composite_layers", a->H, a->W, a->win[l][0], a->win[l][1], a->win[l][2], a->win[l][3])) return rc;
+        if (int rc = check_window("composite_layers", a->H, a->W, win_xy ? 0 : a->win[l][0], win_xy ? 0 : a->win[l][1], a->win[l][2],
+                                  a->win[l][3]))
+            return rc;
     }
-    launch_composite_layers(*a, stream, invalid);
+    if (win_xy != nullptr) launch_composite_layers_at(*a, stream, invalid, win_xy);
+    else launch_composite_layers(*a, stream, invalid);
     return check_launch("composite_layers");
 }
 }  // namespace enerf
@@ -581,6 +588,52 @@ int enerf_composite_prep_indexed(const enerf_composite_prep_t* a, const int* vie
     job.view_idx = view_idx; job.V = V; job.cam_exts = cam_exts; job.cam_ixts = cam_ixts;
     launch_composite_prep(job, (hipStream_t)stream);
     return check_launch("composite_prep_indexed");
+}
+// ---- the windowed kernels with their corners on the device (boxes that move).  What the host can check of a window is its size;
+// the corner is the caller's promise: 0 <= x0 <= w - ww, 0 <= y0 <= h - wh, as the moving frame's preparation launch leaves it ----
+int enerf_build_feature_volume_window_at(const float* feat, const float* proj, const float* depth_values, int B, int S, int C, int Hs,
+                                         int Ws, int D, int h, int w, const int* xy, int ww, int wh, float* vol, enerf_stream_t stream) {
+    REQUIRE(feat && proj && depth_values && vol, "build_feature_volume_window_at: null pointer");
+    REQUIRE(xy, "build_feature_volume_window_at: null xy (two int32 on the device: the window's corner)");
+    REQUIRE(C == 16 || C == 32, "build_feature_volume_window_at: C=%d unsupported (16/32)", C);
+    REQUIRE(B > 0 && S > 0 && Hs > 1 && Ws > 1 && D > 0, "build_feature_volume_window_at: bad shape");
+    if (int rc = check_window("build_feature_volume_window_at", h, w, 0, 0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "build_feature_volume_window_at: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww, D);
+    REQUIRE((long long)B * S * Hs * Ws * C < (1LL << 32) && (long long)Hs * Ws < (1LL << 23),
+            "build_feature_volume_window_at: source features too large for 32-bit gather offsets");
+    REQUIRE((long long)B * D * h * w * (C / 4) < (1LL << 31) && (long long)h * w < (1LL << 23),
+            "build_feature_volume_window_at: grid too large for 32-bit voxel indices");
+    REQUIRE((long long)B * D <= 65535 * 2 && (long long)B * D * h < (1LL << 23) && w < (1 << 23),
+            "build_feature_volume_window_at: B*D=%lld planes / B*D*h=%lld rows beyond the grid-carried voxel decomposition",
+            (long long)B * D, (long long)B * D * h);
+    launch_feature_volume_window_at(feat, proj, depth_values, B, S, C, Hs, Ws, D, h, w, xy, ww, wh, vol, (hipStream_t)stream);
+    return check_launch("build_feature_volume_window_at");
+}
+int enerf_depth_regression_window_at(const float* prob, const float* depth_values, int B, int D, int h, int w, const int* xy, int ww,
+                                     int wh, int depth_inv, float* depth, float* std, enerf_stream_t stream) {
+    REQUIRE(prob && depth_values && depth && std, "depth_regression_window_at: null pointer");
+    REQUIRE(xy, "depth_regression_window_at: null xy (two int32 on the device: the window's corner)");
+    REQUIRE(B > 0 && D > 0 && D <= 64, "depth_regression_window_at: B=%d, D=%d unsupported (D in 1..64)", B, D);
+    if (int rc = check_window("depth_regression_window_at", h, w, 0, 0, ww, wh)) return rc;
+    REQUIRE(wh % 4 == 0 && ww % 4 == 0 && D % 4 == 0, "depth_regression_window_at: wh, ww, D (%d,%d,%d) must be divisible by 4", wh, ww, D);
+    REQUIRE((long long)B * D * h * w < (1LL << 31), "depth_regression_window_at: grid too large");
+    launch_depth_regression_window_at(prob, depth_values, B, D, h, w, xy, ww, wh, depth_inv, depth, std, (hipStream_t)stream);
+    return check_launch("depth_regression_window_at");
+}
+int enerf_composite_layers_at(const enerf_composite_layers_t* a, const int* win_xy, enerf_stream_t stream) {
+    REQUIRE(win_xy, "composite_layers_at: null win_xy ((L,2) int32 on the device: the windows' corners)");
+    return enerf::composite_layers_run_at(a, nullptr, win_xy, (hipStream_t)stream);
+}
+int enerf_layer_boxes(const float* bounds, const float* tar_ext, const float* tar_ixt, int L, int H, int W, const int* sizes,
+                      float near_min, float* xy, float* near_far, int* flags, enerf_stream_t stream) {
+    REQUIRE(bounds && tar_ext && tar_ixt && sizes && xy && near_far && flags, "layer_boxes: null pointer");
+    REQUIRE(L >= 1 && L <= ENERF_MAX_FG_LAYERS, "layer_boxes: L=%d foreground layers unsupported (1..%d)", L, ENERF_MAX_FG_LAYERS);
+    REQUIRE(H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24), "layer_boxes: bad image size H=%d W=%d", H, W);
+    for (int l = 0; l < L; ++l)
+        REQUIRE(sizes[2 * l] > 0 && sizes[2 * l + 1] > 0 && sizes[2 * l] < (1 << 24) && sizes[2 * l + 1] < (1 << 24),
+                "layer_boxes: sizes[%d] = (%d, %d) must be positive", l, sizes[2 * l], sizes[2 * l + 1]);
+    launch_layer_boxes(bounds, tar_ext, tar_ixt, L, H, W, sizes, near_min, xy, near_far, flags, (hipStream_t)stream);
+    return check_launch("layer_boxes");
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 //   * k_composite_layers         parse_layer + raw2outputs_composite (utils.py:875-942): scatter, per-ray depth sort of the
 //                                foreground samples, background appended, alpha compositing — one thread per pixel
 //   * k_composite_layers_bwd     its backward (the training step): the gradients of every layer's and the background's raw samples
+//   * k_depth_regression_window_at, k_composite_layers_at   the two forward kernels with their windows' corners read from device
+//                                memory (boxes that move: prep_job.h resolves the positions, enerf_forward_composite_moving)
 // (The windowed cost volume is k_feature_volume_mp<CQ, true> in volume.hip, the raw-sample render k_render_rays<..., RAW> in
 // render.hip, the backwards of the windowed volume and regression k_feature_volume_bwd<CQ, true> and k_depth_regression_bwd<MK, true>
 // in backward.hip: each is a template value of the kernel it shares its arithmetic with.)
@@ -17,9 +19,10 @@ namespace enerf {
 
 // prob (B, D, wh, ww) of the window at (x0, y0); dv (B, D, h, w); depth / std (B, h, w).  k_depth_regression's mapping (a wave =
 // 16 pixels x 4 depth slices) over the FULL grid; a pixel outside the window runs the same moments with zero logits.
-__global__ __launch_bounds__(256) void k_depth_regression_window(const float* __restrict__ prob, const float* __restrict__ dv, int B,
-                                                                 int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv,
-                                                                 float* __restrict__ depth, float* __restrict__ std) {
+// (depth_regression_window_body is inlined into both kernels: the scalar-argument one compiles to the code it was before the split.)
+__device__ __forceinline__ void depth_regression_window_body(const float* __restrict__ prob, const float* __restrict__ dv, int B,
+                                                             int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv,
+                                                             float* __restrict__ depth, float* __restrict__ std) {
     const int lane = threadIdx.x & 63, sl = lane >> 4;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int hw = h * w, hwp = wh * ww;
@@ -38,6 +41,24 @@ __global__ __launch_bounds__(256) void k_depth_regression_window(const float* __
         depth[i] = mu;
         std[i] = sqrtf(clamp_min(var, 1e-10f));
     }
+}
+__global__ __launch_bounds__(256) void k_depth_regression_window(const float* __restrict__ prob, const float* __restrict__ dv, int B,
+                                                                 int D, int h, int w, int x0, int y0, int ww, int wh, int depth_inv,
+                                                                 float* __restrict__ depth, float* __restrict__ std) {
+    depth_regression_window_body(prob, dv, B, D, h, w, x0, y0, ww, wh, depth_inv, depth, std);
+}
+// the window's corner (x0, y0) = xy[0..1] on the device (moving boxes): one block-uniform load at kernel entry
+__global__ __launch_bounds__(256) void k_depth_regression_window_at(const float* __restrict__ prob, const float* __restrict__ dv, int B,
+                                                                    int D, int h, int w, const int* __restrict__ xy, int ww, int wh,
+                                                                    int depth_inv, float* __restrict__ depth, float* __restrict__ std) {
+    const int x0 = xy[0], y0 = xy[1];
+    depth_regression_window_body(prob, dv, B, D, h, w, x0, y0, ww, wh, depth_inv, depth, std);
+}
+void launch_depth_regression_window_at(const float* prob, const float* dv, int B, int D, int h, int w, const int* xy, int ww, int wh,
+                                       int depth_inv, float* depth, float* std, hipStream_t st) {
+    const long long waves = cdivl((long long)B * h * w, 16);
+    ENERF_LAUNCH(k_depth_regression_window_at, (unsigned)cdivl(waves, 4), 256, 0, st, prob, dv, B, D, h, w, xy, ww, wh, depth_inv, depth,
+                 std);
 }
 void launch_depth_regression_window(const float* prob, const float* dv, int B, int D, int h, int w, int x0, int y0, int ww, int wh,
                                     int depth_inv, float* depth, float* std, hipStream_t st) {
@@ -67,81 +88,33 @@ using CompositeLayers = enerf_composite_layers_t;
 // torch.sort promises none.  The background's Ns samples follow unsorted (utils.py:917-918).
 // `invalid` (nullptr: none) is a device flag of the cached frame: nonzero = a source-view index was outside the cache, and every
 // output of the level is NaN (the ReLUs upstream return 0 for NaN, so the views' NaN alone would reach the colours only).
+// The body is composite_layers_body.h, shared as text with k_composite_layers_at below.
 template <int NFP>
 __global__ __launch_bounds__(256) void k_composite_layers(CompositeLayers a, const int* __restrict__ invalid) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.H * a.W) return;
-    const int y = p / a.W, x = p - y * a.W;
-    const int Ns = a.Ns, nf = a.L * Ns, T = nf + Ns;
-    if (invalid != nullptr && invalid[0] != 0) {        // uniform
-        const float qnan = __int_as_float(0x7fc00000);
-        for (int i = 0; i < nf; ++i) a.z_vals[(long long)p * nf + i] = qnan;
-        for (int t = 0; t < T; ++t) {
-            *reinterpret_cast<float4*>(a.net_output + ((long long)p * T + t) * 4) = make_float4(qnan, qnan, qnan, qnan);
-            a.weights[(long long)p * T + t] = qnan;
-        }
-        a.rgb[(long long)p * 3 + 0] = qnan; a.rgb[(long long)p * 3 + 1] = qnan; a.rgb[(long long)p * 3 + 2] = qnan;
-        a.depth[p] = qnan;
-        return;
-    }
-    int base[ENERF_MAX_FG_LAYERS];                      // the pixel's row in layer l's buffers, or -1
-#pragma unroll
-    for (int l = 0; l < ENERF_MAX_FG_LAYERS; ++l) {
-        const int wx = a.win[l][0], wy = a.win[l][1], ww = a.win[l][2], wh = a.win[l][3];
-        base[l] = (l < a.L && x >= wx && x < wx + ww && y >= wy && y < wy + wh) ? (y - wy) * ww + (x - wx) : -1;
-    }
-    auto row_of = [&](int l) { return l == 0 ? base[0] : (l == 1 ? base[1] : (l == 2 ? base[2] : base[3])); };
-    auto z_of = [&](int l) { return l == 0 ? a.fg_z[0] : (l == 1 ? a.fg_z[1] : (l == 2 ? a.fg_z[2] : a.fg_z[3])); };
-    auto raw_of = [&](int l) { return l == 0 ? a.fg_raw[0] : (l == 1 ? a.fg_raw[1] : (l == 2 ? a.fg_raw[2] : a.fg_raw[3])); };
-    float zk[NFP];
-    int id[NFP];                                        // l * Ns + k of the sample in the slot
-#pragma unroll
-    for (int i = 0; i < NFP; ++i) {
-        zk[i] = INFINITY;
-        id[i] = i;
-        if (i < nf) {
-            const int l = i / Ns, k = i - l * Ns, row = row_of(l);
-            zk[i] = row >= 0 ? z_of(l)[(long long)row * Ns + k] : 0.f;
-            a.z_vals[(long long)p * nf + i] = zk[i];    // z_vals_ori: concatenation order
-        }
-    }
-    if (a.L > 1) {                                      // uniform
-#pragma unroll
-        for (int r = 0; r < NFP; ++r)
-#pragma unroll
-            for (int i = r & 1; i + 1 < NFP; i += 2) {
-                const bool sw = zk[i] > zk[i + 1];
-                const float zl = zk[i], zr = zk[i + 1];
-                const int il = id[i], ir = id[i + 1];
-                zk[i] = sw ? zr : zl; zk[i + 1] = sw ? zl : zr;
-                id[i] = sw ? ir : il; id[i + 1] = sw ? il : ir;
-            }
-    }
-    // alpha compositing (utils.py:922-933): no softmax of the weights
-    float Tacc = 1.f, rgb0 = 0.f, rgb1 = 0.f, rgb2 = 0.f, dep = 0.f, acc = 0.f;
-    auto step = [&](int t, const float4 c, float z) {
-        *reinterpret_cast<float4*>(a.net_output + ((long long)p * T + t) * 4) = c;
-        const float alpha = 1.f - expf(-c.w);
-        const float wgt = alpha * Tacc;
-        Tacc *= (1.f - alpha + 1e-10f);
-        rgb0 += wgt * c.x; rgb1 += wgt * c.y; rgb2 += wgt * c.z;
-        dep += wgt * z;
-        acc += wgt;
-        a.weights[(long long)p * T + t] = wgt;
-    };
-#pragma unroll
-    for (int i = 0; i < NFP; ++i)
-        if (i < nf) {
-            const int l = id[i] / Ns, k = id[i] - l * Ns, row = row_of(l);
-            float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row >= 0) c = *reinterpret_cast<const float4*>(raw_of(l) + ((long long)row * Ns + k) * 4);
-            step(i, c, zk[i]);
-        }
-    for (int k = 0; k < Ns; ++k)
-        step(nf + k, *reinterpret_cast<const float4*>(a.bg_raw + ((long long)p * Ns + k) * 4), a.bg_z[(long long)p * Ns + k]);
-    if (a.white_bkgd) { rgb0 += 1.f - acc; rgb1 += 1.f - acc; rgb2 += 1.f - acc; }
-    a.rgb[(long long)p * 3 + 0] = rgb0; a.rgb[(long long)p * 3 + 1] = rgb1; a.rgb[(long long)p * 3 + 2] = rgb2;
-    a.depth[p] = dep;
+#define ENERF_CL_WIN_X(l) a.win[l][0]
+#define ENERF_CL_WIN_Y(l) a.win[l][1]
+#include "composite_layers_body.h"
+#undef ENERF_CL_WIN_X
+#undef ENERF_CL_WIN_Y
+}
+// Moving boxes (enerf_composite_layers_at): the corners of the L windows are on the device, (x0, y0) of layer l at
+// win_xy[2 * l .. 2 * l + 1] — they replace a.win[l][0..1]; uniform loads at kernel entry and nothing else.
+template <int NFP>
+__global__ __launch_bounds__(256) void k_composite_layers_at(CompositeLayers a, const int* __restrict__ invalid,
+                                                             const int* __restrict__ win_xy) {
+#define ENERF_CL_WIN_X(l) (l < a.L ? win_xy[2 * l] : 0)
+#define ENERF_CL_WIN_Y(l) (l < a.L ? win_xy[2 * l + 1] : 0)
+#include "composite_layers_body.h"
+#undef ENERF_CL_WIN_X
+#undef ENERF_CL_WIN_Y
+}
+void launch_composite_layers_at(const CompositeLayers& a, hipStream_t st, const int* invalid, const int* win_xy) {
+    const int nf = a.L * a.Ns;                          // launch_composite_layers' branch
+    const unsigned grid = (unsigned)cdiv(a.H * a.W, 256);
+    if (nf <= 2) ENERF_LAUNCH_SIMPLE(k_composite_layers_at<2>, grid, 256, 0, st, a, invalid, win_xy);
+    else if (nf <= 4) ENERF_LAUNCH_SIMPLE(k_composite_layers_at<4>, grid, 256, 0, st, a, invalid, win_xy);
+    else if (nf <= 8) ENERF_LAUNCH_SIMPLE(k_composite_layers_at<8>, grid, 256, 0, st, a, invalid, win_xy);
+    else ENERF_LAUNCH_SIMPLE(k_composite_layers_at<16>, grid, 256, 0, st, a, invalid, win_xy);
 }
 void launch_composite_layers(const CompositeLayers& a, hipStream_t st, const int* invalid) {
     const int nf = a.L * a.Ns;

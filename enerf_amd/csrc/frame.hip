@@ -782,6 +782,8 @@ struct CompCascadeLevel {
 struct CompositePlan {
     size_t f_fg[3], f_bg[3], featws_fg, featws_bg, featws_bytes;
     size_t cam_exts, cam_ixts, invalid;    // cached frame: the gathered (1,S,4,4) / (1,S,3,3) camera rows; "an index was outside the cache"
+    size_t wintab;                         // moving boxes: the windows' resolved corners (kWinTableInts ints), then the L flags
+    int bw[ENERF_MAX_FG_LAYERS], bh[ENERF_MAX_FG_LAYERS];     // moving boxes: the layers' sizes in input-image pixels
     CompLevel L[ENERF_MAX_LEVELS];
     CompCascadeLevel C[ENERF_MAX_LEVELS][kCompCascades];
     size_t costreg_ws[kCompCascades], costreg_ws_bytes[kCompCascades];
@@ -799,7 +801,10 @@ int check_comp_window(const char* grid, int level, int l, const int* wn, int h, 
     return ENERF_OK;
 }
 
-int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P, bool cached = false) {
+// `moving` (enerf_forward_composite_moving): the plan depends on the boxes' sizes alone — every window is laid out, and refused, as
+// the box (0, 0, w, h), a box larger than the image is refused, and the workspace gets the table of the corners the preparation
+// launch resolves from the positions on the device.
+int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P, bool cached = false, bool moving = false) {
     REQUIRE(a, "forward_composite: null args");
     const enerf_cascade_t& c = a->cas;
     const int L = a->L;
@@ -846,6 +851,16 @@ int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P,
         P->cam_exts = take((size_t)S * 16);
         P->cam_ixts = take((size_t)S * 9);
         P->invalid = take(64);
+    }
+    if (moving) {
+        for (int l = 0; l < L; ++l) {
+            const float bw = a->bbox[l][2], bh = a->bbox[l][3];
+            REQUIRE(bw >= 1.f && bh >= 1.f && bw <= (float)a->W && bh <= (float)a->H,
+                    "forward_composite_moving: bbox[%d] has the size %g x %g (w, h): w > W, h > H or an empty box in a %d x %d image", l, (double)bw,
+                    (double)bh, a->W, a->H);
+            P->bw[l] = (int)ceilf(bw); P->bh[l] = (int)ceilf(bh);
+        }
+        P->wintab = take(kWinTableInts + ENERF_MAX_FG_LAYERS);
     }
     for (int i = 0; i < c.num; ++i) {
         CompLevel& V = P->L[i];
@@ -897,13 +912,15 @@ int make_composite_plan(const enerf_composite_frame_args_t* a, CompositePlan* P,
                     fg ? "cas.volume_planes" : "bg_volume_planes", i, K.D);
             K.wh = V.h; K.ww = V.w; K.rows = V.render ? V.Hr * V.Wr : 0;
             if (fg) {
-                scaled_box(a->bbox[k], c.volume_scale[i], V.vwin[k]);
+                const float at_origin[4] = {0.f, 0.f, a->bbox[k][2], a->bbox[k][3]};
+                const float* box = moving ? at_origin : a->bbox[k];
+                scaled_box(box, c.volume_scale[i], V.vwin[k]);
                 if (int rc = check_comp_window("volume grid", i, k, V.vwin[k], V.h, V.w)) return rc;
                 K.ww = V.vwin[k][2]; K.wh = V.vwin[k][3];
                 REQUIRE(K.ww % 4 == 0 && K.wh % 4 == 0, "forward_composite: bbox[%d] at level %d is a %d x %d window: ww, wh must be divisible by 4",
                         k, i, K.ww, K.wh);
                 if (V.render) {
-                    scaled_box(a->bbox[k], c.render_scale[i], V.rwin[k]);
+                    scaled_box(box, c.render_scale[i], V.rwin[k]);
                     if (int rc = check_comp_window("ray raster", i, k, V.rwin[k], V.Hr, V.Wr)) return rc;
                     K.rows = V.rwin[k][2] * V.rwin[k][3];
                 }
@@ -958,6 +975,9 @@ struct CompositeRun {
     const enerf_composite_frame_args_t* a = nullptr;
     const enerf_composite_cache_t* cache = nullptr;  // cached frame: the maps, texels and cameras come from here
     const int* view_idx = nullptr;
+    bool moving = false;                 // the boxes' positions are bbox_xy on the device (enerf_forward_composite_moving)
+    const float* bbox_xy = nullptr;
+    int* flags_out = nullptr;
     CompositePlan P;
     hipStream_t st = nullptr;            // the caller's stream
     float* ws = nullptr;
@@ -994,11 +1014,16 @@ struct CompositeRun {
     // the source cameras of the raw renders: the batch's, or (cached frame) the rows the preparation leaves in the workspace
     const float* src_exts() const { return cache ? ws + P.cam_exts : a->src_exts; }
     const float* src_ixts() const { return cache ? ws + P.cam_ixts : a->src_ixts; }
+    // moving boxes: where the preparation leaves layer l's corner at level i (render = 0: volume grid, 1: ray raster); else nullptr
+    const int* corner_of(int i, int render, int l) const {
+        return moving ? reinterpret_cast<const int*>(ws + P.wintab) + win_table_at(i, render, l) : nullptr;
+    }
 
     // the plan, and everything the host can refuse before the first launch
     int begin(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* k, const int* idx, enerf_stream_t stream) {
         a = args; cache = k; view_idx = idx;
-        if (int rc = make_composite_plan(a, &P, cache != nullptr)) return rc;
+        if (int rc = make_composite_plan(a, &P, cache != nullptr, moving)) return rc;
+        if (moving) REQUIRE(bbox_xy, "forward_composite_moving: null bbox_xy (an (L,2) float32 device array: x, y of every layer's box)");
         if (cache != nullptr) {
             if (int rc = check_composite_cache("forward_composite_cached", cache, a->cas, a->H, a->W)) return rc;
             REQUIRE(view_idx, "forward_composite_cached: null view_idx (an (S) int32 device array)");
@@ -1041,6 +1066,20 @@ struct CompositeRun {
         if (cache != nullptr) {
             job.view_idx = view_idx; job.V = cache->V; job.cam_exts = ws + P.cam_exts; job.cam_ixts = ws + P.cam_ixts;
             job.invalid = (int*)(ws + P.invalid);
+        }
+        if (moving) {                                // (job.win[j].level / .layer name the window; its x0, y0 are 0 and unread)
+            MovingBoxes& M = job.mv;
+            M.xy = bbox_xy; M.table = (int*)(ws + P.wintab); M.flags = M.table + kWinTableInts; M.flags_out = flags_out;
+            M.L = L; M.num_levels = c.num; M.H = a->H; M.W = a->W;
+            for (int l = 0; l < L; ++l) { M.bw[l] = P.bw[l]; M.bh[l] = P.bh[l]; }
+            for (int i = 0; i < c.num; ++i) {
+                const CompLevel& V = P.L[i];
+                M.vscale[i] = (float)c.volume_scale[i]; M.rscale[i] = (float)c.render_scale[i];
+                for (int l = 0; l < L; ++l) {
+                    M.vroom[i][l][0] = V.w - V.vwin[l][2]; M.vroom[i][l][1] = V.h - V.vwin[l][3];
+                    M.rroom[i][l][0] = V.render ? V.Wr - V.rwin[l][2] : -1; M.rroom[i][l][1] = V.render ? V.Hr - V.rwin[l][3] : -1;
+                }
+            }
         }
         launch_composite_prep(job, st);
         if (int rc = check_launch("forward_composite: prep")) return rc;
@@ -1125,14 +1164,17 @@ struct CompositeRun {
             rc = enerf_get_depth_values(a->near_far + 2 * k, pdepth[k], pstd[k], pnf[k], 1, K.D, V.h, V.w, hp, wp, V.inv, dv, nf, s);
         if (rc != ENERF_OK) return rc;
         const int* wn = V.vwin[k];
-        rc = fg ? enerf_build_feature_volume_window(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], vol, s)
-                : enerf_build_feature_volume(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, vol, s);
+        const int* at = fg ? corner_of(i, 0, k) : nullptr;         // moving boxes: the corner is read on the device
+        rc = !fg  ? enerf_build_feature_volume(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, vol, s)
+             : at ? enerf_build_feature_volume_window_at(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, at, wn[2], wn[3], vol, s)
+                  : enerf_build_feature_volume_window(feat, proj, dv, 1, a->S, V.C, V.Hs, V.Ws, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], vol, s);
         if (rc != ENERF_OK) return rc;
         rc = cost_reg_run(a->cost_reg_packed[i][k], V.C, 0, vol, 0, 1, K.D, K.wh, K.ww, ws + K.feat3d, prob, ws + P.costreg_ws[k],
                           P.costreg_ws_bytes[k], a->options, s);              // (feat3d: dead work)
         if (rc != ENERF_OK) return rc;
-        rc = fg ? enerf_depth_regression_window(prob, dv, 1, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], V.inv, depth, std, s)
-                : enerf_depth_regression(prob, dv, 1, K.D, V.h, V.w, V.inv, depth, std, s);
+        rc = !fg  ? enerf_depth_regression(prob, dv, 1, K.D, V.h, V.w, V.inv, depth, std, s)
+             : at ? enerf_depth_regression_window_at(prob, dv, 1, K.D, V.h, V.w, at, wn[2], wn[3], V.inv, depth, std, s)
+                  : enerf_depth_regression_window(prob, dv, 1, K.D, V.h, V.w, wn[0], wn[1], wn[2], wn[3], V.inv, depth, std, s);
         pdepth[k] = depth; pstd[k] = std; pnf[k] = nf;
         return rc;
     }
@@ -1167,12 +1209,15 @@ struct CompositeRun {
         m.bg_raw = ws + P.C[i][L].raw; m.bg_z = ws + P.C[i][L].z;
         m.L = L; m.Ns = V.Ns; m.H = V.Hr; m.W = V.Wr; m.white_bkgd = 0;
         m.rgb = a->rgb[i]; m.depth = a->depth[i]; m.weights = a->weights[i]; m.net_output = a->net_output[i]; m.z_vals = a->z_vals[i];
-        return composite_layers_run(&m, cache ? (const int*)(ws + P.invalid) : nullptr, st);      // (uncached: enerf_composite_layers itself)
+        // (uncached, boxes on the host: enerf_composite_layers itself; moving boxes: the L corners of this level's raster, on the device)
+        return composite_layers_run_at(&m, cache ? (const int*)(ws + P.invalid) : nullptr, corner_of(i, 1, 0), st);
     }
 };
 
-int run_composite(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache, const int* view_idx, enerf_stream_t stream) {
+int run_composite(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache, const int* view_idx, enerf_stream_t stream,
+                  bool moving = false, const float* bbox_xy = nullptr, int* flags = nullptr) {
     CompositeRun R;
+    R.moving = moving; R.bbox_xy = bbox_xy; R.flags_out = flags;
     int rc = R.begin(a, cache, view_idx, stream);
     if (rc != ENERF_OK) return rc;
     rc = R.prep();
@@ -1313,6 +1358,28 @@ int enerf_forward_composite_cached(const enerf_composite_frame_args_t* a, const 
                                    enerf_stream_t stream) {
     REQUIRE(cache, "forward_composite_cached: null cache");
     return run_composite(a, cache, view_idx, stream);
+}
+
+// ---- the composite frame with boxes that move: bbox[l][2..3] of the argument block are the sizes (bbox[l][0..1] are ignored), the
+// positions are bbox_xy (L,2) float32 on the device, read by the kernels; flags (L) int32 on the device, optional
+size_t enerf_forward_composite_moving_workspace_bytes(const enerf_composite_frame_args_t* a) {
+    CompositePlan P;
+    if (make_composite_plan(a, &P, false, true) != ENERF_OK) return 0;
+    return P.total_floats * sizeof(float);
+}
+int enerf_forward_composite_moving(const enerf_composite_frame_args_t* a, const float* bbox_xy, int* flags, enerf_stream_t stream) {
+    return run_composite(a, nullptr, nullptr, stream, true, bbox_xy, flags);
+}
+size_t enerf_forward_composite_cached_moving_workspace_bytes(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache) {
+    CompositePlan P;
+    if (make_composite_plan(a, &P, true, true) != ENERF_OK) return 0;
+    if (check_composite_cache("forward_composite_cached", cache, a->cas, a->H, a->W) != ENERF_OK) return 0;
+    return P.total_floats * sizeof(float);
+}
+int enerf_forward_composite_cached_moving(const enerf_composite_frame_args_t* a, const enerf_composite_cache_t* cache, const int* view_idx,
+                                          const float* bbox_xy, int* flags, enerf_stream_t stream) {
+    REQUIRE(cache, "forward_composite_cached: null cache");
+    return run_composite(a, cache, view_idx, stream, true, bbox_xy, flags);
 }
 
 // ---- the composite cache itself: sizes for a cascade, and the build (per net the frame's FeatureNet and texel-pack calls over the V

@@ -336,6 +336,74 @@ void launch_bounds_near_far(const float* vertices, int n, const float* tar_ext, 
 }
 
 // -------------------------------------------------------------------------------------------------
+// The boxes of the composite network's foreground layers for one target camera (enerf_outdoor/enerf.py:156-164, read_tar), so that a
+// captured viewer loop gets its positions without the host.  One block; lane 8 l + c is corner c of layer l in
+// base_utils.get_bound_corners' order (x is bit 2 of c, y bit 1, z bit 0; 0 = the min corner's coordinate), the reductions over a
+// layer's eight corners are three xor-shuffles.
+//   bounds (L,2,3) world min / max corner, tar_ext (1,4,4), tar_ixt (1,3,3), sizes (w, h) per layer (host) ->
+//   xy (L,2) float32, near_far rows 0 .. L-1 = (max(min z, near_min), max z), flags (L)
+// Per layer: camera-space corners R p + t; pixels K c divided by z; rintf (np.round's half-to-even); the rectangle of the eight
+// rounded points clipped to [0, W-1] x [0, H-1]; x = xmin - floor((w - w_ori) / 2), likewise y (enerf.py:163-164).  The final clamp into
+// the image is the frame's (prep_job.h resolve_box_position).  flags: bit 1 = the rectangle is wider or taller than (w, h); bit 2 =
+// a corner has z <= 0 (xy is then (0, 0)); bit 3 = the rectangle misses the image.
+// NOT read_tar's box bit for bit: that is cv2.boundingRect of a cv2.fillPoly raster of the six faces; the rectangle of the rounded
+// corners contains it, so the window never loses content the reference's would keep.
+// -------------------------------------------------------------------------------------------------
+struct LayerBoxSizes { int w[4], h[4]; };
+__global__ __launch_bounds__(64) void k_layer_boxes(const float* __restrict__ bounds, const float* __restrict__ tar_ext,
+                                                    const float* __restrict__ tar_ixt, int L, int H, int W, LayerBoxSizes sz,
+                                                    float near_min, float* __restrict__ xy, float* __restrict__ near_far,
+                                                    int* __restrict__ flags) {
+    const int lane = threadIdx.x, l = min(lane >> 3, L - 1), c = lane & 7;      // (lanes past 8 L shadow the last layer and write nothing)
+    const float* b = bounds + l * 6;
+    const float px = b[((c >> 2) & 1) * 3 + 0], py = b[((c >> 1) & 1) * 3 + 1], pz = b[(c & 1) * 3 + 2];
+    float cam[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float* e = tar_ext + r * 4;
+        cam[r] = add_rn(add_rn(add_rn(mul_rn(e[0], px), mul_rn(e[1], py)), mul_rn(e[2], pz)), e[3]);
+    }
+    const float* K = tar_ixt;
+    const float u = add_rn(add_rn(mul_rn(K[0], cam[0]), mul_rn(K[1], cam[1])), mul_rn(K[2], cam[2]));
+    const float v = add_rn(add_rn(mul_rn(K[3], cam[0]), mul_rn(K[4], cam[1])), mul_rn(K[5], cam[2]));
+    const float z = cam[2];
+    // rounded pixel, kept as a float clamped far inside int range (a corner behind the camera, an overflow: flagged, never an address)
+    const float big = 1.0e9f;
+    const float fx = rintf(u / z), fy = rintf(v / z);
+    float xlo = fx >= -big && fx <= big ? fx : (fx > big ? big : -big), ylo = fy >= -big && fy <= big ? fy : (fy > big ? big : -big);
+    float xhi = xlo, yhi = ylo, zlo = z, zhi = z;
+#pragma unroll
+    for (int m = 4; m >= 1; m >>= 1) {
+        xlo = fminf(xlo, __shfl_xor(xlo, m)); xhi = fmaxf(xhi, __shfl_xor(xhi, m));
+        ylo = fminf(ylo, __shfl_xor(ylo, m)); yhi = fmaxf(yhi, __shfl_xor(yhi, m));
+        zlo = fminf(zlo, __shfl_xor(zlo, m)); zhi = fmaxf(zhi, __shfl_xor(zhi, m));
+    }
+    if (c != 0 || lane >= 8 * L) return;
+    const int w = lane >> 3 == 0 ? sz.w[0] : (lane >> 3 == 1 ? sz.w[1] : (lane >> 3 == 2 ? sz.w[2] : sz.w[3]));
+    const int h = lane >> 3 == 0 ? sz.h[0] : (lane >> 3 == 1 ? sz.h[1] : (lane >> 3 == 2 ? sz.h[2] : sz.h[3]));
+    int f = 0;
+    const bool behind = !(zlo > 0.f);                              // (NaN counts as behind)
+    const int x0 = (int)xlo, x1 = (int)xhi, y0 = (int)ylo, y1 = (int)yhi;
+    if (x1 < 0 || x0 > W - 1 || y1 < 0 || y0 > H - 1) f |= 8;
+    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1), cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
+    const int w_ori = cx1 - cx0 + 1, h_ori = cy1 - cy0 + 1;
+    if (w_ori > w || h_ori > h) f |= 2;
+    float ox = (float)(cx0 - ((w - w_ori) >> 1)), oy = (float)(cy0 - ((h - h_ori) >> 1));       // (>> of a negative: floor, as Python's //)
+    if (behind) { f = 4; ox = 0.f; oy = 0.f; }
+    xy[2 * l] = ox;
+    xy[2 * l + 1] = oy;
+    near_far[2 * l] = fmaxf(zlo, near_min);
+    near_far[2 * l + 1] = zhi;
+    flags[l] = f;
+}
+void launch_layer_boxes(const float* bounds, const float* tar_ext, const float* tar_ixt, int L, int H, int W, const int* sizes,
+                        float near_min, float* xy, float* near_far, int* flags, hipStream_t st) {
+    LayerBoxSizes sz = {};
+    for (int l = 0; l < L; ++l) { sz.w[l] = sizes[2 * l]; sz.h[l] = sizes[2 * l + 1]; }
+    ENERF_LAUNCH(k_layer_boxes, 1u, 64, 0, st, bounds, tar_ext, tar_ixt, L, H, W, sz, near_min, xy, near_far, flags);
+}
+
+// -------------------------------------------------------------------------------------------------
 // gui_human.py:88-91:  img *= 255; img.to(uint8); flip(0)   — rgb (H*W,3) float -> (H,W,3) uint8
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pack_rgb8(const float* __restrict__ rgb, int H, int W, int flip,

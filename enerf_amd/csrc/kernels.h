@@ -352,5 +352,17 @@ void launch_composite_layers_bwd(const enerf_composite_layers_bwd_t& g, hipStrea
 struct CompositePrep;
 int composite_prep_job(const enerf_composite_prep_t* a, CompositePrep* job);
 void launch_composite_prep(const CompositePrep& job, hipStream_t st);
+// boxes that move (enerf_forward_composite_moving): the windowed kernels with their corners read on the device — xy = (x0, y0) of the
+// window, win_xy = (x0, y0) per layer — as the preparation launch resolved them (prep_job.h, MovingBoxes)
+void launch_feature_volume_window_at(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs, int Ws, int D,
+                                     int h, int w, const int* xy, int ww, int wh, float* vol, hipStream_t st);
+void launch_depth_regression_window_at(const float* prob, const float* dv, int B, int D, int h, int w, const int* xy, int ww, int wh,
+                                       int depth_inv, float* depth, float* std, hipStream_t st);
+void launch_composite_layers_at(const enerf_composite_layers_t& a, hipStream_t st, const int* invalid, const int* win_xy);
+// enerf_composite_layers_at / the moving frame's merge: composite_layers_run with the corners on the device (win_xy == nullptr: as above)
+int composite_layers_run_at(const enerf_composite_layers_t* a, const int* invalid, const int* win_xy, hipStream_t st);
+// the layers' boxes of a target camera on the device (io.hip k_layer_boxes)
+void launch_layer_boxes(const float* bounds, const float* tar_ext, const float* tar_ixt, int L, int H, int W, const int* sizes,
+                        float near_min, float* xy, float* near_far, int* flags, hipStream_t st);
 
 }  // namespace enerf

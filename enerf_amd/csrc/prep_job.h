@@ -104,11 +104,73 @@ __device__ __forceinline__ void prep_job_block(const PrepJob& J, int vb, int tid
 constexpr int kCompositePrepCascades = 5;        // ENERF_MAX_FG_LAYERS + 1
 constexpr int kCompositePrepWindows = 12;        // ENERF_MAX_LEVELS * ENERF_MAX_FG_LAYERS
 constexpr int kCompositePrepJobBlocks = 32;
+
+// ---- boxes that move (enerf_forward_composite_moving): the layers' sizes (w, h) are the host's and part of the plan, their positions
+// (x, y) are two float32 per layer in input-image pixels that the kernels read themselves.  ONE function resolves a position, so every
+// user gets the same bits: a non-finite value becomes 0, the value is truncated toward zero and clamped to [0, extent - size] (the
+// clamp of enerf_outdoor/enerf.py:165-168); *changed is set if any of that changed the value.  extent >= size (the plan checks).
+__device__ __forceinline__ int resolve_box_position(float v, int size, int extent, bool* changed) {
+    const bool finite = fabsf(v) <= 3.402823466e38f;               // false for NaN and +-inf
+    const float f = finite ? truncf(v) : 0.f;
+    const float hi = (float)(extent - size);                       // extents < 2^24: exact
+    const float c = fminf(fmaxf(f, 0.f), hi);
+    *changed = !(c == v);
+    return (int)c;
+}
+// the corner of the layer's window in a level's grid: (int)((float)xi * (float)scale), a float32 product without contraction, then
+// truncation — scaled_box of frame.hip, (bbox * scale).int() of the reference.  `room` = grid extent - window extent >= 0: for the
+// scales the cascade uses (powers of two) the corner never exceeds it; for any other scale the min keeps a rounded product inside.
+__device__ __forceinline__ int scaled_box_corner(int xi, float scale, int room) {
+    const int c = (int)((float)xi * scale);                        // (a lone product: nothing to contract it with)
+    return c < room ? c : room;
+}
+constexpr int kWinTableInts = 3 * 2 * 4 * 2;     // int win[ENERF_MAX_LEVELS][volume | render][ENERF_MAX_FG_LAYERS][2]
+__host__ __device__ inline int win_table_at(int level, int render, int layer) { return ((level * 2 + render) * 4 + layer) * 2; }
+// what the preparation needs to resolve every window of a frame whose positions are on the device
+struct MovingBoxes {
+    const float* xy;                 // (L, 2) float32 on the device; nullptr: the windows are the job's scalars, as ever
+    int* table;                      // the resolved corners, kWinTableInts ints (win_table_at); unrendered levels' render rows are 0
+    int* flags;                      // (L): bit 0 = the position was changed by the resolution
+    int* flags_out;                  // optional copy of the flags for the caller (nullptr: none)
+    int L, num_levels, H, W;
+    int bw[4], bh[4];                // the layers' sizes in input-image pixels
+    float vscale[3], rscale[3];      // volume_scale / render_scale per level
+    int vroom[3][4][2], rroom[3][4][2];   // grid extent - window extent per level and layer, (x, y); rroom < 0: the level is not rendered
+};
+__device__ __forceinline__ void resolve_window(const MovingBoxes& M, int level, int render, int l, int* x0, int* y0, bool* changed) {
+    bool cx, cy;
+    const int xi = resolve_box_position(M.xy[2 * l + 0], M.bw[l], M.W, &cx);
+    const int yi = resolve_box_position(M.xy[2 * l + 1], M.bh[l], M.H, &cy);
+    const float sc = render ? M.rscale[level] : M.vscale[level];
+    const int* room = render ? M.rroom[level][l] : M.vroom[level][l];
+    *x0 = scaled_box_corner(xi, sc, room[0]);
+    *y0 = scaled_box_corner(yi, sc, room[1]);
+    *changed = cx || cy;
+}
+// block 0 of a job with moving boxes: the table and the flags, plain stores
+__device__ __forceinline__ void composite_prep_window_table(const MovingBoxes& M, int tid, int threads) {
+    for (int e = tid; e < 3 * 2 * 4; e += threads) {
+        const int level = e / 8, render = (e >> 2) & 1, l = e & 3;
+        int x0 = 0, y0 = 0;
+        bool changed;
+        if (level < M.num_levels && l < M.L && !(render && M.rroom[level][l][0] < 0)) resolve_window(M, level, render, l, &x0, &y0, &changed);
+        M.table[win_table_at(level, render, l)] = x0;
+        M.table[win_table_at(level, render, l) + 1] = y0;
+    }
+    if (tid < M.L) {
+        int x0, y0;
+        bool changed;
+        resolve_window(M, 0, 0, tid, &x0, &y0, &changed);
+        M.flags[tid] = changed ? 1 : 0;
+        if (M.flags_out != nullptr) M.flags_out[tid] = changed ? 1 : 0;
+    }
+}
+
 struct CompositePrep {
     ProjJob pj[3];                                // proj == nullptr: none
     struct Planes { const float* near_far; float *dv, *nf; int D, block0, blocks; } cas[kCompositePrepCascades];
     int n_cas, h, w, depth_inv;
-    struct Window { int x0, y0, ww, wh, Wr, block0, blocks; int *index, *count; } win[kCompositePrepWindows];
+    struct Window { int x0, y0, ww, wh, Wr, block0, blocks; int *index, *count; int level, layer; } win[kCompositePrepWindows];
     int n_win;
     int nblocks;
     // A cached frame (enerf_forward_composite_cached, enerf_composite_prep_indexed): the source cameras sit in a cache's tables behind a
@@ -120,6 +182,10 @@ struct CompositePrep {
     int V;
     float *cam_exts, *cam_ixts;
     int* invalid;
+    // Moving boxes (enerf_forward_composite_moving): mv.xy != nullptr.  A block that writes a window's ray list resolves the window
+    // itself (resolve_window: a handful of integer operations, no exchange between blocks), block 0 also writes the table the
+    // frame's windowed kernels read and the flags.  mv.xy == nullptr: x0, y0 of every Window as given.
+    MovingBoxes mv;
 };
 inline int composite_prep_job_blocks(long long elements, int threads) {
     const long long nb = (elements + threads - 1) / threads;
@@ -165,6 +231,7 @@ __device__ __forceinline__ void composite_prep_block(const CompositePrep& J, int
                     proj_one(q, J.pj[l].src_ixts, J.pj[l].src_exts, J.pj[l].tar_ixt, J.pj[l].tar_ext, J.pj[l].S, J.pj[l].src_scale,
                              J.pj[l].tar_scale, J.pj[l].proj);
     }
+    if (vb == 0 && J.mv.xy != nullptr) composite_prep_window_table(J.mv, tid, threads);
     const int hw = J.h * J.w;
 #pragma unroll 1
     for (int c = 0; c < J.n_cas; ++c) {
@@ -182,9 +249,14 @@ __device__ __forceinline__ void composite_prep_block(const CompositePrep& J, int
         const CompositePrep::Window& Wn = J.win[j];
         if (vb < Wn.block0 || vb >= Wn.block0 + Wn.blocks) continue;
         if (vb == Wn.block0 && tid == 0) Wn.count[0] = Wn.ww * Wn.wh;
+        int x0 = Wn.x0, y0 = Wn.y0;
+        if (J.mv.xy != nullptr) {                                   // uniform
+            bool changed;
+            resolve_window(J.mv, Wn.level, 1, Wn.layer, &x0, &y0, &changed);
+        }
         for (int i = (vb - Wn.block0) * threads + tid; i < Wn.ww * Wn.wh; i += Wn.blocks * threads) {
             const int yy = i / Wn.ww, xx = i - yy * Wn.ww;
-            Wn.index[i] = (Wn.y0 + yy) * Wn.Wr + Wn.x0 + xx;
+            Wn.index[i] = (y0 + yy) * Wn.Wr + x0 + xx;
         }
         return;
     }

@@ -139,11 +139,18 @@ __global__ __launch_bounds__(256) void k_feature_volume(const float* __restrict_
 // WIN (the composite network's boxed layers, homo_warp_composite utils.py:153-190): (h, w) is a WINDOW of the (hf, wf) grid with its
 // corner at (x0, y0).  The block -> voxel decomposition and the output (B, D, h, w, C) are the window's; the depth planes dv are
 // read at, and the pixel projected from, the voxel's place in the FULL grid — every voxel gets the bits the full launch gives it.
-template <int CQ, bool WIN = false>
+// AT (WIN only; a composite frame whose boxes move, enerf_forward_composite_moving): the corner is read from device memory, (x0, y0) =
+// xy[0..1] — what the preparation launch resolved and clamped (prep_job.h) — by one block-uniform load at kernel entry and nothing
+// else; the arguments x0, y0 are unread.  A template value, so that the instantiations with the corner in the arguments keep the
+// instruction stream they had before it existed (xy is an argument they never load).
+template <int CQ, bool WIN = false, bool AT = false>
 __global__ __launch_bounds__(256) void k_feature_volume_mp(const float* __restrict__ feat, const float* __restrict__ proj,
                                                            const float* __restrict__ dv, int B, int S, int Hs, int Ws,
                                                            int D, int h, int w, float inv_w, float inv_d, int planar,
-                                                           float* __restrict__ vol, int x0, int y0, int hf, int wf) {
+                                                           float* __restrict__ vol, int x0, int y0, int hf, int wf,
+                                                           const int* __restrict__ xy) {
+    static_assert(WIN || !AT, "a corner on the device belongs to a window");
+    if constexpr (AT) { x0 = xy[0]; y0 = xy[1]; }
     constexpr int C = CQ * 4, NPL = 2;
     const int xcd = blockIdx.x;                                    // gridDim.x == 8: one row band per XCD (see above)
     const int rb = (h + 7) >> 3;
@@ -249,9 +256,9 @@ void launch_feature_volume(const float* feat_nhwc, const float* proj, const floa
     if (ENERF_VOL_NPL == 2 && D % 2 == 0) {                       // two planes per wave
         const dim3 grid2(8, (unsigned)cdiv(rb * w, vpb), (unsigned)(B * D / 2));
         switch (C) {
-            case 32: ENERF_LAUNCH(k_feature_volume_mp<8>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
-            case 16: ENERF_LAUNCH(k_feature_volume_mp<4>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
-            case 8: ENERF_LAUNCH(k_feature_volume_mp<2>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w); return;
+            case 32: ENERF_LAUNCH(k_feature_volume_mp<8>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w, nullptr); return;
+            case 16: ENERF_LAUNCH(k_feature_volume_mp<4>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w, nullptr); return;
+            case 8: ENERF_LAUNCH(k_feature_volume_mp<2>, grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, h, w, inv_w, inv_d, planar, vol, 0, 0, h, w, nullptr); return;
             default: return;   // validated by the C-ABI layer
         }
     }
@@ -272,8 +279,21 @@ void launch_feature_volume_window(const float* feat_nhwc, const float* proj, con
     const float inv_w = 1.f / (float)ww, inv_d = 1.f / (float)D;
     const dim3 grid2(8, (unsigned)cdiv(rb * ww, vpb), (unsigned)(B * D / 2));
     switch (C) {
-        case 32: ENERF_LAUNCH((k_feature_volume_mp<8, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w); break;
-        case 16: ENERF_LAUNCH((k_feature_volume_mp<4, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w); break;
+        case 32: ENERF_LAUNCH((k_feature_volume_mp<8, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w, nullptr); break;
+        case 16: ENERF_LAUNCH((k_feature_volume_mp<4, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, x0, y0, h, w, nullptr); break;
+        default: break;   // validated by the C-ABI layer
+    }
+}
+// ... with the corner (x0, y0) = xy[0..1] read on the device
+void launch_feature_volume_window_at(const float* feat_nhwc, const float* proj, const float* dv, int B, int S, int C, int Hs, int Ws, int D,
+                                     int h, int w, const int* xy, int ww, int wh, float* vol, hipStream_t st) {
+    const int rb = (wh + 7) / 8;
+    const int vpb = 256 / (C / 4);
+    const float inv_w = 1.f / (float)ww, inv_d = 1.f / (float)D;
+    const dim3 grid2(8, (unsigned)cdiv(rb * ww, vpb), (unsigned)(B * D / 2));
+    switch (C) {
+        case 32: ENERF_LAUNCH((k_feature_volume_mp<8, true, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, 0, 0, h, w, xy); break;
+        case 16: ENERF_LAUNCH((k_feature_volume_mp<4, true, true>), grid2, 256, 0, st, feat_nhwc, proj, dv, B, S, Hs, Ws, D, wh, ww, inv_w, inv_d, 0, vol, 0, 0, h, w, xy); break;
         default: break;   // validated by the C-ABI layer
     }
 }

@@ -28,8 +28,16 @@ class GraphedFrame:
             raise RuntimeError("GraphedFrame: the human variant needs static_shapes=True (no count readback inside a graph)")
         # the composite network (network_composite.py) reads its boxes on the host: a device tensor would be a readback inside the
         # capture, and the boxes' windows are baked into the captured launches
+        # With batch['bbox_size'] (+ batch['bbox_xy'], a device tensor, or positions ``fn`` computes itself, e.g. EnerfLib.layer_boxes)
+        # only the sizes are baked in: the positions are read by the kernels, and a replay with moved boxes is legal.
         self.composite = hasattr(net, "num_fg_layers")
-        if self.composite:
+        self.moving = self.composite and net._is_moving(batch)
+        if self.moving:
+            xy = batch.get("bbox_xy")
+            if xy is not None and not (torch.is_tensor(xy) and xy.is_cuda):
+                raise RuntimeError("GraphedFrame: batch['bbox_xy'] must be a device tensor (an upload inside the capture is not replayed)")
+            self._sizes = net._sizes(batch)
+        elif self.composite:
             if torch.is_tensor(batch.get("bbox")) and batch["bbox"].is_cuda:
                 raise RuntimeError("GraphedFrame: the composite network needs batch['bbox'] on the host (a CPU tensor or a sequence); "
                                    "a device tensor is a readback inside the capture")
@@ -67,7 +75,11 @@ class GraphedFrame:
             if ent is None or (ent if self.composite else ent[0]) is not t:
                 raise RuntimeError("GraphedFrame: the network's weights changed (load_state_dict / .to()) after capture; "
                                    "re-capture the frame")
-        if self.composite and self.net._boxes(batch) != self._boxes:
+        if self.moving:
+            if not self.net._is_moving(batch) or self.net._sizes(batch) != self._sizes:
+                raise RuntimeError("GraphedFrame: batch['bbox_size'] changed; the boxes' sizes are part of the captured launches: re-capture "
+                                   "(the positions, batch['bbox_xy'], may move freely)")
+        elif self.composite and (self.net._is_moving(batch) or self.net._boxes(batch) != self._boxes):
             raise RuntimeError("GraphedFrame: batch['bbox'] changed; the boxes' windows are part of the captured launches: re-capture")
         for k, v in batch.items():
             if torch.is_tensor(v):

@@ -365,6 +365,15 @@ _SIGNATURES = {
     "enerf_composite_prep_indexed": (_i, [C.POINTER(CompositePrepArgs), C.c_void_p, _i, _f, _f, _f]),
     "enerf_forward_composite_cached_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct)]),
     "enerf_forward_composite_cached": (_i, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct), C.c_void_p, _f]),
+    "enerf_build_feature_volume_window_at": (_i, [_f, _f, _f] + [_i] * 8 + [C.c_void_p, _i, _i, _f, _f]),
+    "enerf_depth_regression_window_at": (_i, [_f, _f] + [_i] * 4 + [C.c_void_p, _i, _i, _i, _f, _f, _f]),
+    "enerf_composite_layers_at": (_i, [C.POINTER(CompositeLayersArgs), C.c_void_p, _f]),
+    "enerf_layer_boxes": (_i, [_f, _f, _f, _i, _i, _i, C.POINTER(_i), _fl, _f, _f, C.c_void_p, _f]),
+    "enerf_forward_composite_moving_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs)]),
+    "enerf_forward_composite_moving": (_i, [C.POINTER(CompositeFrameArgs), _f, C.c_void_p, _f]),
+    "enerf_forward_composite_cached_moving_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct)]),
+    "enerf_forward_composite_cached_moving": (_i, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct), C.c_void_p, _f,
+                                                   C.c_void_p, _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -875,6 +884,107 @@ class EnerfLib:
 
     def forward_composite_cached(self, args: "CompositeFrameArgs", cache: "CompositeCacheStruct", view_idx_ptr, stream):
         self._check(self.dll.enerf_forward_composite_cached(C.byref(args), C.byref(cache), view_idx_ptr, stream), "forward_composite_cached")
+
+    # -- the composite network with boxes that move: sizes on the host, positions on the device (include/enerf_hip.h) ----------
+    @staticmethod
+    def _corner(xy, n, what):
+        if not torch.is_tensor(xy) or xy.dtype != torch.int32 or not xy.is_contiguous() or xy.numel() != n:
+            raise EnerfError(f"{what}: the corner(s) must be a contiguous int32 device tensor of {n} values")
+        return xy
+
+    def build_feature_volume_window_at(self, feat_cl, proj, dv, Cc, xy, size, out=None):
+        """:meth:`build_feature_volume_window` with the window's corner ``xy`` = (x0, y0), two int32 on the device, and its extent
+        ``size`` = (ww, wh) on the host.  The corner must lie inside the grid (0 <= x0 <= w - ww, 0 <= y0 <= h - wh)."""
+        B, S, Hs, Ws = feat_cl.shape[:4]
+        _, D, h, w = dv.shape
+        ww, wh = (int(v) for v in size)
+        self._corner(xy, 2, "build_feature_volume_window_at")
+        vol = _out(out, (B, D, max(wh, 0), max(ww, 0), Cc), dv.device, "build_feature_volume_window_at")
+        self._check(self.dll.enerf_build_feature_volume_window_at(_ptr(feat_cl), _ptr(proj), _ptr(dv), B, S, Cc, Hs, Ws, D, h, w,
+                                                                  xy.data_ptr(), ww, wh, _ptr(vol), self.stream_of(vol)),
+                    "build_feature_volume_window_at")
+        return vol
+
+    def depth_regression_window_at(self, prob, dv, depth_inv, xy, size, out=None):
+        """:meth:`depth_regression_window` with the corner ``xy`` (two int32) on the device and ``size`` = (ww, wh) on the host."""
+        B, D, h, w = dv.shape
+        ww, wh = (int(v) for v in size)
+        self._corner(xy, 2, "depth_regression_window_at")
+        if tuple(prob.shape) != (B, D, wh, ww):
+            raise EnerfError(f"depth_regression_window_at: prob {tuple(prob.shape)} is not (B, D, wh, ww) = {(B, D, wh, ww)}")
+        depth = _out(None if out is None else out[0], (B, h, w), dv.device, "depth_regression_window_at")
+        std = _out(None if out is None else out[1], (B, h, w), dv.device, "depth_regression_window_at")
+        self._check(self.dll.enerf_depth_regression_window_at(_ptr(prob), _ptr(dv), B, D, h, w, xy.data_ptr(), ww, wh, int(depth_inv),
+                                                              _ptr(depth), _ptr(std), self.stream_of(dv)), "depth_regression_window_at")
+        return depth, std
+
+    def composite_layers_at(self, fg, win_xy, sizes, bg, H, W, white_bkgd=False):
+        """:meth:`composite_layers` with the L windows' corners ``win_xy`` (L,2) int32 on the device and their extents ``sizes`` =
+        [(ww, wh)] on the host."""
+        L, (bg_raw, bg_z) = len(fg), bg
+        Ns, N, dev = int(bg_z.shape[-1]), H * W, bg_z.device
+        if L > MAX_FG_LAYERS or len(sizes) != L:
+            raise EnerfError(f"composite_layers_at: {L} foreground layers, {len(sizes)} sizes (at most {MAX_FG_LAYERS}, one size each)")
+        self._corner(win_xy, 2 * L, "composite_layers_at")
+        if bg_raw.numel() != N * Ns * 4 or bg_z.numel() != N * Ns:
+            raise EnerfError("composite_layers_at: the background covers the whole (H, W) image")
+        a = CompositeLayersArgs(L=L, Ns=Ns, H=int(H), W=int(W), white_bkgd=int(bool(white_bkgd)))
+        for l, ((raw, z), (ww, wh)) in enumerate(zip(fg, sizes)):
+            if raw.numel() != max(ww * wh, 0) * Ns * 4 or z.numel() != max(ww * wh, 0) * Ns:
+                raise EnerfError(f"composite_layers_at: layer {l}: buffers do not hold the window's {ww}x{wh} pixels x {Ns} samples")
+            a.fg_raw[l], a.fg_z[l] = _ptr(raw), _ptr(z)
+            a.win[l][2], a.win[l][3] = int(ww), int(wh)
+        T = (L + 1) * Ns
+        shapes = {"rgb": (N, 3), "depth": (N,), "weights": (N, T), "net_output": (N, T, 4), "z_vals": (N, L * Ns)}
+        res = {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in shapes.items()}
+        for k in shapes:
+            setattr(a, k, _ptr(res[k]))
+        a.bg_raw, a.bg_z = _ptr(bg_raw), _ptr(bg_z)
+        self._check(self.dll.enerf_composite_layers_at(C.byref(a), win_xy.data_ptr(), self.stream_of(bg_z)), "composite_layers_at")
+        return res
+
+    def layer_boxes(self, bounds, tar_ext, tar_ixt, H, W, sizes, near_min=0.0, out=None):
+        """The foreground layers' box positions for a target camera, on the device (``enerf_layer_boxes``; read_tar of
+        enerf_outdoor/enerf.py:156-164 with the rectangle of the rounded corners in place of cv2's raster, which it contains):
+        ``bounds`` (L,2,3) world min / max corner per layer, ``tar_ext`` (1,4,4), ``tar_ixt`` (1,3,3), ``sizes`` = [(w, h)] per
+        layer on the host.  Returns ``(xy (L,2) float32, near_far (L+1,2), flags (L) int32)``: ``xy`` is what ``batch['bbox_xy']``
+        takes; rows 0..L-1 of ``near_far`` = (max(min z, near_min), max z), the background's row is left as it is (``out`` =
+        (xy, near_far, flags) to fill existing tensors, e.g. a near_far whose last row the caller has set).  flags: bit 1 = the
+        projected rectangle is larger than the size, bit 2 = a corner is behind the camera (xy = (0, 0)), bit 3 = it misses the
+        image.  Nothing is read on the host."""
+        L, dev = int(bounds.shape[0]), bounds.device
+        sizes = [(int(w), int(h)) for w, h in sizes]
+        if tuple(bounds.shape) != (L, 2, 3) or tar_ext.numel() != 16 or tar_ixt.numel() != 9 or len(sizes) != L:
+            raise EnerfError(f"layer_boxes: bounds (L,2,3), tar_ext (1,4,4), tar_ixt (1,3,3) and L sizes, got {tuple(bounds.shape)} / "
+                             f"{tuple(tar_ext.shape)} / {tuple(tar_ixt.shape)} / {len(sizes)}")
+        for t in (bounds, tar_ext, tar_ixt):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise EnerfError("layer_boxes: bounds, tar_ext and tar_ixt must be contiguous float32 tensors on one device")
+        if out is None:
+            out = (torch.empty((L, 2), dtype=torch.float32, device=dev), torch.zeros((L + 1, 2), dtype=torch.float32, device=dev),
+                   torch.empty((L,), dtype=torch.int32, device=dev))
+        xy, near_far, flags = out
+        if xy.dtype != torch.float32 or xy.numel() != 2 * L or near_far.dtype != torch.float32 or near_far.numel() != 2 * (L + 1) or \
+                flags.dtype != torch.int32 or flags.numel() != L or not (xy.is_contiguous() and near_far.is_contiguous()):
+            raise EnerfError("layer_boxes: out = (xy (L,2) float32, near_far (L+1,2) float32, flags (L) int32), contiguous")
+        host = (_i * (2 * max(L, 1)))(*[v for s_ in sizes for v in s_])
+        self._check(self.dll.enerf_layer_boxes(_ptr(bounds), _ptr(tar_ext), _ptr(tar_ixt), L, int(H), int(W), host, float(near_min),
+                                               _ptr(xy), _ptr(near_far), flags.data_ptr(), self.stream_of(bounds)), "layer_boxes")
+        return xy, near_far, flags
+
+    def forward_composite_moving_workspace_bytes(self, args: "CompositeFrameArgs", cache: "CompositeCacheStruct" = None) -> int:
+        n = (self.dll.enerf_forward_composite_moving_workspace_bytes(C.byref(args)) if cache is None else
+             self.dll.enerf_forward_composite_cached_moving_workspace_bytes(C.byref(args), C.byref(cache)))
+        if n == 0:
+            raise EnerfError(f"forward_composite_moving: {self.dll.enerf_last_error().decode()}")
+        return n
+
+    def forward_composite_moving(self, args: "CompositeFrameArgs", bbox_xy_ptr, flags_ptr, stream, cache=None, view_idx_ptr=None):
+        if cache is None:
+            self._check(self.dll.enerf_forward_composite_moving(C.byref(args), bbox_xy_ptr, flags_ptr, stream), "forward_composite_moving")
+        else:
+            self._check(self.dll.enerf_forward_composite_cached_moving(C.byref(args), C.byref(cache), view_idx_ptr, bbox_xy_ptr, flags_ptr,
+                                                                       stream), "forward_composite_cached_moving")
 
     # -- backward kernels (training path; wrapped by enerf_amd/autograd.py) -----------------------------
     def build_feature_volume_bwd(self, feat_cl, proj, dv, grad_vol):

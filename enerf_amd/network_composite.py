@@ -42,6 +42,15 @@ overwrites what this one returned; clone what must outlive it.  The last ``MAX_S
 
 Host synchronisation: the boxes are read on the host.  ``batch['bbox']`` as a CPU tensor or a sequence costs nothing; as a device
 tensor that read is the frame's ONE synchronisation.  Nothing after it waits for the device.
+
+Boxes that move (a moving actor, a moving camera): ``batch['bbox_size']`` — a host sequence of ``(w, h)`` per layer — together with
+``batch['bbox_xy']`` — a float32 DEVICE tensor (L,2) or (1,L,2) of ``(x, y)`` — instead of ``batch['bbox']``.  The sizes are part
+of the frame's shape, the positions are read by the kernels (``enerf_forward_composite_moving``): a moved box is the same shape —
+no new buffers, no new plan — the position is never read on the host, and a ``GraphedFrame`` replays with moved boxes.  A position
+is resolved on the device: non-finite -> 0, truncated, clamped into the image; ``intermediates['bbox_flags']`` (L) int32 on the
+device has bit 0 set for every layer whose position that changed.  For positions ``bbox`` accepts the outputs are its bits.
+``EnerfLib.layer_boxes`` computes the positions of a target camera on the device.  One C call per frame only: ``driver="staged"``,
+a ``stage_hook`` and the training path refuse such a batch.
 """
 from __future__ import annotations
 
@@ -197,6 +206,41 @@ class Network(nn.Module):
             raise ValueError(f"network_composite: batch['bbox'] must hold (x, y, w, h) for {self.num_fg_layers} layers")
         return [tuple(b) for b in bbox[:self.num_fg_layers]]
 
+    @staticmethod
+    def _is_moving(batch):
+        return batch.get("bbox_size") is not None or batch.get("bbox_xy") is not None
+
+    def _sizes(self, batch):
+        """``batch['bbox_size']``: the layers' (w, h), read on the host — a sequence or a CPU tensor, never a device tensor."""
+        if batch.get("bbox") is not None:
+            raise ValueError("network_composite: pass either batch['bbox'] or batch['bbox_size'] with batch['bbox_xy'], not both")
+        size = batch.get("bbox_size")
+        if size is None:
+            raise ValueError("network_composite: batch['bbox_xy'] needs batch['bbox_size'], the (w, h) of every layer on the host")
+        if torch.is_tensor(size):
+            if size.is_cuda:
+                raise ValueError("network_composite: batch['bbox_size'] must be on the host (a sequence or a CPU tensor): the sizes are "
+                                 "part of the frame's shape")
+            size = size.reshape(-1, 2).tolist()
+        elif len(size) == 1 and len(size[0]) and hasattr(size[0][0], "__len__"):
+            size = size[0]
+        if len(size) != self.num_fg_layers or any(len(b) != 2 for b in size):
+            raise ValueError(f"network_composite: batch['bbox_size'] must hold (w, h) for {self.num_fg_layers} layers")
+        return tuple((float(w), float(h)) for w, h in size)
+
+    def _positions(self, batch, held):
+        """``batch['bbox_xy']`` as the (L,2) float32 device tensor the kernels read: used in place if it is one, otherwise converted
+        and uploaded into the shape's buffer first (as ``view_idx`` is).  Never read on the host."""
+        xy = batch.get("bbox_xy")
+        if xy is None:
+            raise ValueError("network_composite: batch['bbox_size'] needs batch['bbox_xy'], the (x, y) of every layer")
+        if not torch.is_tensor(xy):
+            xy = torch.tensor(xy, dtype=torch.float32)
+        L = self.num_fg_layers
+        if xy.numel() != 2 * L or tuple(xy.shape) not in ((L, 2), (1, L, 2)):
+            raise ValueError(f"network_composite: batch['bbox_xy'] must be ({L}, 2) or (1, {L}, 2)")
+        return held("bbox_xy", xy, (L, 2))
+
     def _shape_buffers(self, key):
         """The buffers of one frame shape — (H, W, S, boxes, which levels bring their own rays, device) — allocated on the first frame of that shape and reused by every
         later one; the few most recent shapes are kept (moving boxes change the windowed buffers' sizes)."""
@@ -247,6 +291,9 @@ class Network(nn.Module):
             if not getattr(self, "trainable", False):
                 raise RuntimeError("network_composite: inference only — forward() has no training path unless the network was built "
                                    "with trainable=True; call net.eval()")
+            if self._is_moving(batch):
+                raise ValueError("network_composite: the training path takes batch['bbox'] only; batch['bbox_size'] / batch['bbox_xy'] "
+                                 "(positions on the device) are for inference")
             from .train_path_composite import forward_train_composite
             self.invalidate_packed()                   # the optimizer is about to change what the packed images (and a source cache) hold
             return forward_train_composite(self, batch)
@@ -255,14 +302,19 @@ class Network(nn.Module):
         B, S, _, H, W = src.shape
         if B != 1:
             raise ValueError("network_composite: B must be 1 (the reference reads batch['bbox'][0] for every batch element)")
-        boxes = self._boxes(batch)
+        moving = self._is_moving(batch)
+        if moving and (self.driver != "call" or self.stage_hook is not None):
+            raise RuntimeError("network_composite: batch['bbox_size'] / batch['bbox_xy'] (positions on the device) have no staged form: "
+                               "use driver='call' and clear stage_hook")
+        boxes = [(0.0, 0.0, w, h) for w, h in self._sizes(batch)] if moving else self._boxes(batch)
         dev = src.device
         near_far = batch["near_far"]
         if tuple(near_far.shape) != (1, L + 1, 2):
             raise ValueError(f"network_composite: near_far must be (1, {L + 1}, 2): one range per foreground layer, the background's last")
         # (generated rays live in the frame's workspace: a batch with and one without rays_{i} are two shapes)
         own_rays = tuple(batch.get(f"rays_{i}") is not None for i in range(cas.num))
-        st, buf = self._shape_buffers((H, W, S, tuple(boxes), own_rays, dev))
+        st, buf = self._shape_buffers(("moving", H, W, S, tuple(b[2:] for b in boxes), own_rays, dev) if moving
+                                      else (H, W, S, tuple(boxes), own_rays, dev))
         hook = self.stage_hook if self.stage_hook is not None else (lambda name: None)
         held = self._holder(buf, dev)
         exts, ixts = held("src_exts", batch["src_exts"], (1, S, 4, 4)), held("src_ixts", batch["src_ixts"], (1, S, 3, 3))
@@ -272,7 +324,8 @@ class Network(nn.Module):
         nfs = buf("near_far", (L + 1, 1, 2))                        # one contiguous (1, 2) range per cascade
         nfs.copy_(near_far.reshape(L + 1, 1, 2))
         if self.driver == "call" and self.stage_hook is None:
-            return self._forward_call(batch, st, buf, held, boxes, (src4, bg4, exts, ixts, tar_ext, tar_ixt, nfs), S, H, W)
+            return self._forward_call(batch, st, buf, held, boxes, (src4, bg4, exts, ixts, tar_ext, tar_ixt, nfs), S, H, W,
+                                      bbox_xy=self._positions(batch, held) if moving else None)
         hook("begin")
         feats, feats_bg = [], []
         for name, into in (("feature_net", feats), ("feature_net_bg", feats_bg)):           # both read src_inps (network_composite.py:78-79)
@@ -391,23 +444,28 @@ class Network(nn.Module):
         if batch["tar_ext"].device != dev:
             raise ValueError("forward_cached: cache and batch must live on one device")
         S, H, W = int(view_idx.numel()), cache.H, cache.W
-        boxes = self._boxes(batch)
+        moving = self._is_moving(batch)
+        boxes = [(0.0, 0.0, w, h) for w, h in self._sizes(batch)] if moving else self._boxes(batch)
         near_far = batch["near_far"]
         if tuple(near_far.shape) != (1, L + 1, 2):
             raise ValueError(f"network_composite: near_far must be (1, {L + 1}, 2): one range per foreground layer, the background's last")
         own_rays = tuple(batch.get(f"rays_{i}") is not None for i in range(self.cfg.cas.num))
-        st, buf = self._shape_buffers(("cached", H, W, S, tuple(boxes), own_rays, dev))
+        st, buf = self._shape_buffers(("cached-moving", H, W, S, tuple(b[2:] for b in boxes), own_rays, dev) if moving
+                                      else ("cached", H, W, S, tuple(boxes), own_rays, dev))
         held = self._holder(buf, dev)
         tar_ext, tar_ixt = held("tar_ext", batch["tar_ext"], (1, 4, 4)), held("tar_ixt", batch["tar_ixt"], (1, 3, 3))
         nfs = buf("near_far", (L + 1, 1, 2))
         nfs.copy_(near_far.reshape(L + 1, 1, 2))
-        return self._forward_call(batch, st, buf, held, boxes, (None, None, None, None, tar_ext, tar_ixt, nfs), S, H, W, cache, view_idx)
+        return self._forward_call(batch, st, buf, held, boxes, (None, None, None, None, tar_ext, tar_ixt, nfs), S, H, W, cache, view_idx,
+                                  bbox_xy=self._positions(batch, held) if moving else None)
 
-    def _forward_call(self, batch, st, buf, held, boxes, inputs, S, H, W, cache=None, view_idx=None):
+    def _forward_call(self, batch, st, buf, held, boxes, inputs, S, H, W, cache=None, view_idx=None, bbox_xy=None):
         """The frame as ONE C call (enerf_forward_composite): the shape's outputs, depth / std maps and one workspace tensor are handed
         to the driver, which runs the stages of the staged path below ``forward`` itself — same kernels, same bits — with the
         foreground layers forked onto the library's side lane unless ``options.single_stream``.  With ``cache`` and ``view_idx`` it is
-        the cached frame (enerf_forward_composite_cached): no images, source cameras or FeatureNet weights in the argument block."""
+        the cached frame (enerf_forward_composite_cached): no images, source cameras or FeatureNet weights in the argument block.
+        With ``bbox_xy`` (the (L,2) float32 device tensor of a batch with ``bbox_size``) ``boxes`` are (0, 0, w, h), the shape is keyed
+        by the sizes and the entry is enerf_forward_composite_moving / _cached_moving, which reads the positions on the device."""
         cas, lib, L = self.cfg.cas, self.lib, self.num_fg_layers
         whos = [f"layer{l}" for l in range(L)] + ["bg"]
         a = st.get("call.args")
@@ -455,10 +513,19 @@ class Network(nn.Module):
         opts = self.options                              # (kept alive by self for the length of the call)
         a.options = None if opts is None else C.pointer(opts)
         if "call.args" not in st:                        # one workspace per shape, sized by the plan (which refuses a bad frame here)
-            nbytes = lib.forward_composite_workspace_bytes(a) if cache is None else lib.forward_composite_cached_workspace_bytes(a, cache.struct)
+            if bbox_xy is not None:
+                nbytes = lib.forward_composite_moving_workspace_bytes(a, None if cache is None else cache.struct)
+            else:
+                nbytes = lib.forward_composite_workspace_bytes(a) if cache is None else lib.forward_composite_cached_workspace_bytes(a, cache.struct)
             ws = buf("call.ws", ((nbytes + 3) // 4,))
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
             st["call.args"] = a
+        if bbox_xy is not None:
+            flags = buf("bbox_flags", (L,), torch.int32)
+            lib.forward_composite_moving(a, bbox_xy.data_ptr(), flags.data_ptr(), lib.stream_of(tar_ext),
+                                         None if cache is None else cache.struct, None if cache is None else view_idx.data_ptr())
+            self.intermediates = dict(st["call.inter"], bbox_flags=flags)
+            return dict(st["call.outs"])
         if cache is None:
             lib.forward_composite(a, lib.stream_of(src4))
         else:

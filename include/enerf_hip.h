@@ -1024,6 +1024,58 @@ size_t enerf_forward_composite_cached_workspace_bytes(const enerf_composite_fram
 int enerf_forward_composite_cached(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* cache, const int* view_idx,
                                    enerf_stream_t stream);
 
+/* ---- the composite network with boxes that move (ABI v11 grew by these eight entries; new symbols only, the version number is
+ * unchanged).  In enerf_outdoor/actor1.yaml the box (x, y, w, h) of every foreground layer changes with every camera and time frame;
+ * the dataset rounds w and h up to multiples of 32 (enerf_outdoor/enerf.py:161-162), so the SIZE takes few values and belongs to the
+ * frame's shape, while the POSITION is continuous and belongs to the frame.  These entries take the sizes on the host and the
+ * positions as a small device array the kernels read themselves: a moved box is neither a new plan nor a new captured graph.
+ *
+ *   enerf_forward_composite_moving, enerf_forward_composite_cached_moving (+ their _workspace_bytes)
+ *       enerf_forward_composite / enerf_forward_composite_cached with args->bbox[l][2..3] = the sizes (w, h) of layer l —
+ *       args->bbox[l][0..1] are ignored — and bbox_xy (L,2) float32 on the device = (x, y) of every layer in input-image pixels.
+ *       The plan depends on the sizes alone: every refusal of the entries above, evaluated for the box (0, 0, w, h), plus w > W,
+ *       h > H (or a size below 1) and a null bbox_xy.  The preparation launch resolves each position on the device, the same
+ *       function for every user: a non-finite value becomes 0; the value is truncated toward zero; it is clamped to [0, W - w] /
+ *       [0, H - h] (the clamp of enerf.py:165-168).  Per level the window's corner is (int)((float)x * (float)scale), a float32
+ *       product and a truncation as (bbox * scale).int() of the reference, with volume_scale for the cost volume and render_scale
+ *       for the rays; the windows' extents come from (w, h) on the host as ever.  After the clamp no position can produce an address
+ *       outside a grid, whatever bbox_xy holds (for a scale that is no power of two the corner is also kept at most
+ *       grid extent - window extent).  flags (L) int32 on the device, optional (NULL: none): bit 0 of flags[l] is set if the
+ *       resolution changed layer l's position (it was non-finite, fractional or outside the image).  Everything from the cascades
+ *       on is the driver of the entries above — same kernels, same fork — with the windowed volume, the windowed regression and
+ *       the merge in their _at forms below; for positions the host entries accept, every output holds the host entries' bits.
+ *   enerf_build_feature_volume_window_at, enerf_depth_regression_window_at
+ *       the entries without _at with the window's corner (x0, y0) = xy[0..1], two int32 on the device: a block-uniform load at
+ *       kernel entry, the same arithmetic after it.  The host checks the window's extent (ww, wh) against the grid; the corner is
+ *       the caller's promise, 0 <= x0 <= w - ww and 0 <= y0 <= h - wh, as the moving frame's preparation leaves it.
+ *   enerf_composite_layers_at
+ *       enerf_composite_layers with the L corners win_xy (L,2) int32 on the device; args->win[l][0..1] are ignored.
+ *   enerf_layer_boxes
+ *       the positions for a target camera without the host (read_tar, enerf_outdoor/enerf.py:156-164), one wave: bounds (L,2,3) =
+ *       world min / max corner per layer, tar_ext (1,4,4), tar_ixt (1,3,3), sizes = (w, h) per layer on the HOST, 2 L ints.  Per
+ *       layer, in this order: the eight corners (base_utils.get_bound_corners' order) in camera space, R p + t; pixels K c
+ *       divided by z; rintf (np.round's half-to-even); the rectangle of the eight rounded points clipped to [0, W-1] x [0, H-1],
+ *       w_ori x h_ori; x = xmin - floor((w - w_ori) / 2), likewise y.  Outputs: xy (L,2) float32 — what enerf_forward_composite_moving
+ *       takes, which does the final clamp —; rows 0 .. L-1 of near_far (L+1,2) = (max(min z, near_min), max z), the background's
+ *       row is not touched; flags (L) int32: bit 1 = the rectangle is wider or taller than (w, h), content is cut; bit 2 = a
+ *       corner has z <= 0, xy is then (0, 0) and no other bit is set; bit 3 = the rectangle misses the image.
+ *       This is NOT read_tar's box bit for bit: read_tar takes cv2.boundingRect of a cv2.fillPoly raster of the box's faces.
+ *       The rectangle of the rounded corners contains that raster's rectangle, so the window never loses content the reference's
+ *       would keep. */
+int enerf_build_feature_volume_window_at(const float* feat, const float* proj, const float* depth_values, int B, int S, int C, int Hs,
+                                         int Ws, int D, int h, int w, const int* xy, int ww, int wh, float* vol, enerf_stream_t stream);
+int enerf_depth_regression_window_at(const float* prob, const float* depth_values, int B, int D, int h, int w, const int* xy, int ww,
+                                     int wh, int depth_inv, float* depth, float* std, enerf_stream_t stream);
+int enerf_composite_layers_at(const enerf_composite_layers_t* args, const int* win_xy, enerf_stream_t stream);
+int enerf_layer_boxes(const float* bounds, const float* tar_ext, const float* tar_ixt, int L, int H, int W, const int* sizes,
+                      float near_min, float* xy, float* near_far, int* flags, enerf_stream_t stream);
+size_t enerf_forward_composite_moving_workspace_bytes(const enerf_composite_frame_args_t* args);
+int enerf_forward_composite_moving(const enerf_composite_frame_args_t* args, const float* bbox_xy, int* flags, enerf_stream_t stream);
+size_t enerf_forward_composite_cached_moving_workspace_bytes(const enerf_composite_frame_args_t* args,
+                                                             const enerf_composite_cache_t* cache);
+int enerf_forward_composite_cached_moving(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* cache,
+                                          const int* view_idx, const float* bbox_xy, int* flags, enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
