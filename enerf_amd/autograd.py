@@ -399,8 +399,8 @@ class _Block:
     """One Conv3d/ConvTranspose3d + BatchNorm3d (+ ReLU) (+ skip add) in training mode.  ``images``: the packed weight images
     of the forward layer and of its input-gradient layer (pack_plan.cost_reg_plan: one gather launch per network and step)."""
 
-    def __init__(self, lib, w, bn, kind, relu, images):
-        self.lib, self.w, self.kind = lib, w, kind
+    def __init__(self, lib, w, bn, kind, relu, images, options=None):
+        self.lib, self.w, self.kind, self.options = lib, w, kind, options
         self.norm = _BatchNormTrain(lib, bn, relu)
         self.pk_fwd, self.pk_bwd = images
         if kind == _T2:
@@ -411,23 +411,23 @@ class _Block:
     def forward(self, x, residual=None):
         lib = self.lib
         self.x = x
-        z = lib.conv3d_layer(self.pk_fwd, self.cin, self.cout, self.kind, x)
+        z = lib.conv3d_layer(self.pk_fwd, self.cin, self.cout, self.kind, x, options=self.options)
         return self.norm.forward(z, residual)
 
     def backward(self, g, add=None):
         """g = gradient w.r.t. the block's output (the skip branch's share is the same tensor); ``add``: a tensor of the input's
         shape added to the input gradient in the convolution's epilogue (the skip branch's gradient of the block's input).
         Returns (grad_input (+ add), grad_weight, grad_bn_weight, grad_bn_bias)."""
-        lib = self.lib
+        lib, opt = self.lib, self.options
         dz, dgamma, dbeta = self.norm.backward(g)
         if self.kind == _S1:                                                         # dgrad: flipped, channel-transposed weights
-            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _S1, dz, residual=add)
+            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _S1, dz, residual=add, options=opt)
             gw = lib.conv_wgrad_cl(dz, self.x, 1)
         elif self.kind == _S2:                                                       # dgrad of a stride-2 conv = transposed conv on w
-            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _T2, dz, residual=add)
+            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _T2, dz, residual=add, options=opt)
             gw = lib.conv_wgrad_cl(dz, self.x, 2)
         else:                                                                        # dgrad of a transposed conv = stride-2 conv on w
-            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _S2, dz, residual=add)
+            gx = lib.conv3d_layer(self.pk_bwd, self.cout, self.cin, _S2, dz, residual=add, options=opt)
             gw = lib.conv_wgrad_cl(self.x, dz, 2)
         return gx, gw, dgamma, dbeta
 
@@ -440,15 +440,16 @@ class CostRegTrainFn(torch.autograd.Function):
         x = vol.permute(0, 2, 3, 4, 1).contiguous()                                   # channels-last (a view of FeatureVolumeFn's output)
         blk = {}
         img = pack_plan.plan_of(lib, m, pack_plan.cost_reg_plan, x.device).run()     # every weight image of the step: one launch
+        opt = getattr(ctx, "options", None)                                          # cost_reg_train(..., options=): the conv kernels' route
 
         def cbr(i, kind):
             mod = getattr(m, f"conv{i}")
-            blk[i] = _Block(lib, mod.conv.weight, mod.bn, kind, True, (img[i, "fwd"], img[i, "bwd"]))
+            blk[i] = _Block(lib, mod.conv.weight, mod.bn, kind, True, (img[i, "fwd"], img[i, "bwd"]), opt)
             return blk[i]
 
         def up(i):
             mod = getattr(m, f"conv{i}")
-            blk[i] = _Block(lib, mod[0].weight, mod[1], _T2, False, (img[i, "fwd"], img[i, "bwd"]))
+            blk[i] = _Block(lib, mod[0].weight, mod[1], _T2, False, (img[i, "fwd"], img[i, "bwd"]), opt)
             return blk[i]
         c0 = cbr(0, _S1).forward(x)
         c2 = cbr(2, _S1).forward(cbr(1, _S2).forward(c0))
@@ -460,7 +461,7 @@ class CostRegTrainFn(torch.autograd.Function):
         y = up(9).forward(y, residual=c2)
         y = up(11).forward(y, residual=c0)
         # heads: feat_conv (8 -> 8) ++ depth_conv (8 -> 1) as one 8 -> 16 layer (rows 9..15 zero)
-        heads = lib.conv3d_layer(img["heads", "fwd"], 8, 16, _S1, y)
+        heads = lib.conv3d_layer(img["heads", "fwd"], 8, 16, _S1, y, options=opt)
         ctx.lib, ctx.m, ctx.blk, ctx.y, ctx.heads_bwd = lib, m, blk, y, img["heads", "bwd"]
         feat = lib.slice_channels(heads, 0, 8).permute(0, 4, 1, 2, 3)      # contiguous channels-last (what the render-side fetch reads)
         prob = lib.slice_channels(heads, 8, 1)[..., 0]                     # contiguous (B,D,h,w)
@@ -477,7 +478,7 @@ class CostRegTrainFn(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, g16):
         lib, m, blk, y = ctx.lib, ctx.m, ctx.blk, ctx.y
-        g = lib.conv3d_layer(ctx.heads_bwd, 16, 8, _S1, g16)                         # d y11
+        g = lib.conv3d_layer(ctx.heads_bwd, 16, 8, _S1, g16, options=getattr(ctx, "options", None))     # d y11
         gw16 = lib.conv_wgrad_cl(g16, y, 1)
         grads = {"feat": gw16[:8], "depth": gw16[8:9]}
 
@@ -506,8 +507,25 @@ class CostRegTrainFn(torch.autograd.Function):
         return (None, None, g_x.permute(0, 4, 1, 2, 3)) + tuple(out)
 
 
-def cost_reg_train(lib, m, vol):
-    """Apply CostRegTrainFn with the module's parameters as differentiable inputs (fixed order)."""
+def check_cost_reg_train_shape(full: bool, B: int, D: int, h: int, w: int):
+    """What the training blocks need of a cost volume (B, C, D, h, w), checked on the host before anything is launched.  Every
+    stride-2 level must halve exactly: an odd size comes back from the transposed layer one voxel larger (2 * ceil(n / 2)) than
+    the skip tensor the BatchNorm's affine kernel reads beside it, where the reference's ``c2 + conv9(...)`` raises a size
+    mismatch.  And every BatchNorm needs more than one position per channel, as torch's."""
+    levels = 3 if full else 2
+    div = 1 << levels
+    if D % div or h % div or w % div:
+        raise ValueError(f"cost_reg_train: D,h,w ({D},{h},{w}) must be divisible by {div}")
+    deepest = (B * D * h * w) >> (3 * levels)
+    if deepest <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"{[B, 64 if full else 32, D // div, h // div, w // div]}")
+
+
+def cost_reg_train(lib, m, vol, options=None):
+    """Apply CostRegTrainFn with the module's parameters as differentiable inputs (fixed order).  ``options``: the ``lib.Options`` every
+    convolution and input-gradient layer is routed with (None: the library's defaults)."""
+    check_cost_reg_train_shape(bool(m.full), vol.shape[0], *vol.shape[2:])
     order = [0, 1, 2, 3, 4] + ([5, 6, 7] if m.full else []) + [9, 11, "feat", "depth"]
     params = []
     for i in order:
@@ -523,7 +541,7 @@ def cost_reg_train(lib, m, vol):
     class _Fn(CostRegTrainFn):
         @staticmethod
         def forward(ctx, *a):
-            ctx.order = order
+            ctx.order, ctx.options = order, options
             return CostRegTrainFn.forward(ctx, *a)
     return _Fn.apply(lib, m, vol, *params)
 

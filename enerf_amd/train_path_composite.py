@@ -14,7 +14,8 @@ inference path already uses and a backward kernel of its own:
 Per cascade and level: ``get_depth_values`` with the cascade's own row of ``batch['near_far']`` (``DepthValuesFn`` after level 0: the
 masked in-place clamps pass the gradient through the un-clamped branch only, ``near_far`` detached; a level after a depth-space level
 raises, as in ``forward_train``), the (windowed) volume, the MinCostRegNet through ``cost_reg_train`` — batch statistics over the
-window's voxels, running statistics updated as the reference's modules update them; with frozen BatchNorm (``bn.eval()``) through the
+window's voxels, running statistics updated as the reference's modules update them (a window whose ``D``, ``wh`` or ``ww`` is not
+divisible by 4 is refused by layer and window before its volume is built); with frozen BatchNorm (``bn.eval()``) through the
 modules —, the (windowed) regression, and on a rendered level ``RaySamplesFn`` + ``TexelsFn`` + ``GatherFn`` + the fused MLP on the
 cascade's rays.  Both FeatureNets run through ``feature_net_forward``.
 
@@ -70,7 +71,7 @@ def forward_train_composite(net, batch: Dict[str, torch.Tensor]) -> Dict[str, to
     ``z_vals`` — both returned DETACHED: they are the sorted samples and the concatenated sample depths, data movement the loss
     does not read — each suffixed ``_level{i}``; no ``idx`` (see the module docstring of network_composite.py)."""
     from .autograd import (CompositeLayersFn, DepthRegressionFn, DepthValuesFn, FeatureVolumeFn, GatherFn, RaySamplesFn, TexelsFn,
-                           WindowDepthRegressionFn, WindowFeatureVolumeFn, cost_reg_train, nerf_mlp)
+                           WindowDepthRegressionFn, WindowFeatureVolumeFn, check_cost_reg_train_shape, cost_reg_train, nerf_mlp)
     from .network_composite import BG_PLANES, _scaled_box
     from .train_path import _hip_lib, _need, camera_tables, cost_reg_forward, feature_net_forward
     cas, L = net.cfg.cas, net.num_fg_layers
@@ -121,10 +122,17 @@ def forward_train_composite(net, batch: Dict[str, torch.Tensor]) -> Dict[str, to
                 if not cas.depth_inv[i - 1]:
                     raise RuntimeError("cascade levels after a depth-space level are undefined in the reference (utils.py:130)")
                 dv, nf = DepthValuesFn.apply(lib, *prev[c], nf_rows[c], D, hv, wv, inv)
-            vol = FeatureVolumeFn.apply(lib, feat, P, dv) if win is None else WindowFeatureVolumeFn.apply(lib, feat, P, dv, win)
             reg = getattr(net, f"cost_reg_{i}_{who}")
+            bn_batch = all(m.training for m in reg.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm))
+            if bn_batch:                    # a window is int(bbox * scale): any size.  Refused here, by name, before its volume is built
+                try:
+                    check_cost_reg_train_shape(bool(reg.full), 1, D, *((hv, wv) if win is None else (win[3], win[2])))
+                except ValueError as e:
+                    where = "the full grid" if win is None else f"window (x0, y0, ww, wh) = {tuple(win)}"
+                    raise ValueError(f"network_composite: cost_reg_{i}_{who}, {where} of the {hv} x {wv} level-{i} grid: {e}") from None
+            vol = FeatureVolumeFn.apply(lib, feat, P, dv) if win is None else WindowFeatureVolumeFn.apply(lib, feat, P, dv, win)
             # batch statistics on the HIP training blocks; frozen BatchNorm (bn.eval()) through the modules, as in forward_train
-            if all(m.training for m in reg.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
+            if bn_batch:
                 _, prob = cost_reg_train(lib, reg, vol)
             else:
                 _, prob = cost_reg_forward(reg, vol, lib)
