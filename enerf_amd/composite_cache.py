@@ -31,9 +31,13 @@ class CompositeSourceCache:
 
     ``inps`` / ``bg_inps`` are either float images, (V,3,H,W) float32 in [-1,1], or what a camera / decoder delivers, (V,H,W,3)
     uint8: those go through ``enerf_ingest_views_u8`` (no mask) first.  The reference's ``read_data_bg`` reads one static
-    background image per camera, so a :meth:`rebuild` without ``bg_inps`` keeps the images of the last build."""
+    background image per camera, so a :meth:`rebuild` without ``bg_inps`` keeps the images of the last build.  With ``raw`` (a
+    :class:`enerf_amd.raw_ingest.RawIngest`) uint8 images, the background's too, are RAW frames (V,Hraw,Wraw,3): they go through
+    ``enerf_ingest_raw_u8`` (read_data / read_data_bg of enerf_outdoor/enerf.py:107-152), the cache's H and W are the rig's and
+    ``ixts`` are ``raw.ixts``."""
 
-    def __init__(self, net, inps: torch.Tensor, bg_inps: torch.Tensor, exts: torch.Tensor, ixts: torch.Tensor, chunk: int = 0):
+    def __init__(self, net, inps: torch.Tensor, bg_inps: torch.Tensor, exts: torch.Tensor, ixts: torch.Tensor, chunk: int = 0, raw=None):
+        self._raw = raw
         V, H, W = self._image_shape(inps)
         self._allocate(net, V, H, W, exts, ixts, chunk)
         self.rebuild(inps, bg_inps)
@@ -43,11 +47,14 @@ class CompositeSourceCache:
         """The buffers of a cache for V views of HxW with nothing in them yet: :meth:`rebuild` (with ``bg_inps``) fills them
         (``packed_gen`` is -1 until then, so ``forward_cached`` refuses the empty cache)."""
         self = cls.__new__(cls)
+        self._raw = None
         self._allocate(net, V, H, W, exts, ixts, chunk)
         return self
 
-    @staticmethod
-    def _image_shape(inps):
+    def _image_shape(self, inps):
+        if self._raw is not None and inps.dtype == torch.uint8:
+            self._raw.check_frame(inps, what="cache_sources (raw)")
+            return inps.shape[0], self._raw.H, self._raw.W
         if inps.dim() == 4 and inps.dtype == torch.uint8 and inps.shape[3] == 3:
             return inps.shape[0], inps.shape[1], inps.shape[2]
         if inps.dim() != 4 or inps.shape[1] != 3 or inps.dtype == torch.uint8:
@@ -90,6 +97,8 @@ class CompositeSourceCache:
                              f"{tuple(inps.shape)}; build a new cache for another V, H or W")
         if inps.device != self.device:
             raise ValueError("CompositeSourceCache.rebuild: the images must live on the cache's device")
+        if inps.dtype == torch.uint8 and self._raw is not None:
+            return self._raw(inps, lib=lib)
         if inps.dtype == torch.uint8:
             return lib.ingest_views_u8(inps.contiguous())
         return inps.contiguous()

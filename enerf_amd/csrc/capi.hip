@@ -1039,6 +1039,32 @@ int enerf_ingest_views_u8(const unsigned char* img, const unsigned char* mask, i
     launch_ingest_views_u8(img, mask, dilate, V, H, W, out, (hipStream_t)stream);
     return check_launch("ingest_views_u8");
 }
+int enerf_ingest_raw_geometry(int Hraw, int Wraw, double input_ratio, int* Hs, int* Ws) {
+    REQUIRE(Hs && Ws, "ingest_raw_geometry: null %s", Hs ? "Ws" : "Hs");
+    REQUIRE(Hraw >= 1 && Wraw >= 1 && Hraw <= 32768 && Wraw <= 32768, "ingest_raw_geometry: bad raw extent %dx%d (1..32768)", Hraw, Wraw);
+    REQUIRE(input_ratio >= 0.25 && input_ratio <= 1.0, "ingest_raw_geometry: input_ratio=%g (0.25..1)", input_ratio);
+    ingest_raw_geometry(Hraw, Wraw, input_ratio, Hs, Ws);
+    return ENERF_OK;
+}
+int enerf_ingest_raw_u8(const unsigned char* img, const unsigned char* mask, const float* ixts, const float* dist, int V, int Hraw,
+                        int Wraw, double input_ratio, int crop_y, int crop_x, int H, int W, int dilate, unsigned char* mask_scratch,
+                        float* out, unsigned char* mask_out, enerf_stream_t stream) {
+    REQUIRE(img && out, "ingest_raw_u8: null %s", img ? "out" : "img");
+    REQUIRE(V >= 1 && V <= 65535, "ingest_raw_u8: V=%d views (1..65535)", V);
+    REQUIRE(Hraw >= 1 && Wraw >= 1 && Hraw <= 32768 && Wraw <= 32768, "ingest_raw_u8: bad raw extent %dx%d (1..32768)", Hraw, Wraw);
+    REQUIRE(input_ratio >= 0.25 && input_ratio <= 1.0, "ingest_raw_u8: input_ratio=%g (0.25..1)", input_ratio);   // (NaN fails too)
+    REQUIRE(dilate == 0 || (dilate % 2 == 1 && dilate >= 3 && dilate <= 9), "ingest_raw_u8: dilate=%d (0, or an odd box size 3..9)", dilate);
+    int Hs = 0, Ws = 0;
+    ingest_raw_geometry(Hraw, Wraw, input_ratio, &Hs, &Ws);
+    REQUIRE(H >= 1 && W >= 1 && crop_y >= 0 && crop_x >= 0 && crop_y <= Hs - H && crop_x <= Ws - W,
+            "ingest_raw_u8: crop (y0=%d, x0=%d, %dx%d) leaves the resized image %dx%d", crop_y, crop_x, H, W, Hs, Ws);
+    REQUIRE(dist == nullptr || ixts != nullptr, "ingest_raw_u8: dist without ixts");
+    REQUIRE(mask != nullptr || mask_out == nullptr, "ingest_raw_u8: mask_out without a mask");
+    REQUIRE(!(dilate > 0 && mask != nullptr && mask_scratch == nullptr), "ingest_raw_u8: dilate=%d with a mask needs mask_scratch (V,Hraw,Wraw)", dilate);
+    launch_ingest_raw_u8(img, mask, ixts, dist, V, Hraw, Wraw, input_ratio, crop_y, crop_x, H, W, dilate, mask_scratch, out, mask_out,
+                         (hipStream_t)stream);
+    return check_launch("ingest_raw_u8");
+}
 int enerf_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
                           enerf_stream_t stream) {
     REQUIRE(vertices && tar_ext && near_far, "bounds_near_far: null pointer");

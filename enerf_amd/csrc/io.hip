@@ -694,3 +694,5 @@ void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* ma
 #include "lpips_vgg.h"
 // Trainer's perceptual term (losses/vgg_perceptual_loss.py:21-37): the same trunk's first ten layers, forward and backward
 #include "perceptual_vgg.h"
+// Raw camera frames (undistort, area resize, crop) to the float image of the source-view caches (enerf_outdoor/enerf.py:129-152)
+#include "ingest_raw.h"

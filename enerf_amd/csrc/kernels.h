@@ -310,6 +310,10 @@ void launch_rays_bbox_mask(const float* rays, const float* bounds, long long n, 
 void launch_select_views(const float* cam_points, int V, const float* c2w, int k, int* idx, hipStream_t st);
 void launch_gather_views(const float* inps, const float* exts, const float* ixts, const int* idx, int k, int H, int W,
                          float* src_inps, float* src_exts, float* src_ixts, hipStream_t st);
+void ingest_raw_geometry(int Hraw, int Wraw, double input_ratio, int* Hs, int* Ws);
+void launch_ingest_raw_u8(const unsigned char* img, const unsigned char* mask, const float* ixts, const float* dist, int V, int Hraw,
+                          int Wraw, double input_ratio, int crop_y, int crop_x, int H, int W, int dilate, unsigned char* mask_scratch,
+                          float* out, unsigned char* mask_out, hipStream_t st);
 void launch_ingest_views_u8(const unsigned char* img, const unsigned char* mask, int dilate, int V, int H, int W, float* out,
                             hipStream_t st);
 void launch_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,

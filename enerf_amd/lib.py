@@ -346,6 +346,8 @@ _SIGNATURES = {
     "enerf_forward_cached_workspace_bytes": (C.c_size_t, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct)]),
     "enerf_forward_cached": (_i, [C.POINTER(FrameArgs), C.POINTER(SourceCacheStruct), C.c_void_p, _f]),
     "enerf_ingest_views_u8": (_i, [C.c_void_p, C.c_void_p, _i, _i, _i, _i, _f, _f]),
+    "enerf_ingest_raw_u8": (_i, [C.c_void_p, C.c_void_p, _f, _f, _i, _i, _i, C.c_double, _i, _i, _i, _i, _i, C.c_void_p, _f, C.c_void_p, _f]),
+    "enerf_ingest_raw_geometry": (_i, [_i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i)]),
     "enerf_bounds_near_far": (_i, [_f, _i, _f, _i, _fl, _f, _f]),
     "enerf_build_feature_volume_window": (_i, [_f, _f, _f] + [_i] * 12 + [_f, _f]),
     "enerf_depth_regression_window": (_i, [_f, _f] + [_i] * 9 + [_f, _f, _f]),
@@ -1709,6 +1711,54 @@ class EnerfLib:
         self._check(self.dll.enerf_ingest_views_u8(img.data_ptr(), None if mask is None else mask.data_ptr(), int(dilate), V, H, W,
                                                    _ptr(out), self.stream_of(img)),
                     "ingest_views_u8")
+        return out
+
+    def ingest_raw_geometry(self, Hraw, Wraw, input_ratio=1.0):
+        """(Hs, Ws) of a raw Hraw x Wraw frame resized by ``input_ratio``: rounded half-to-even, the C side's one rounding."""
+        hs, ws = C.c_int(0), C.c_int(0)
+        self._check(self.dll.enerf_ingest_raw_geometry(int(Hraw), int(Wraw), float(input_ratio), C.byref(hs), C.byref(ws)),
+                    "ingest_raw_geometry")
+        return hs.value, ws.value
+
+    def ingest_raw_u8(self, img, ixts=None, dist=None, mask=None, dilate=0, input_ratio=1.0, crop=None, scratch=None, out=None,
+                      mask_out=None):
+        """Raw camera frames to the caches' float image on the device (zjumocap/enerf_interactive.py:116-135, enerf_outdoor/enerf.py:
+        129-152): img (V,Hraw,Wraw,3) uint8, ixts (V,3,3) and dist (V,5) = (k1,k2,p1,p2,k3) float32 (dist None: no undistortion),
+        mask (V,Hraw,Wraw) uint8 / bool or None, ``crop`` = (y0, x0, H, W) in the image resized by ``input_ratio`` (None: all of it)
+        -> (V,3,H,W) float32 in [-1,1]; ``mask_out`` (V,H,W) uint8 receives the final mask.  ``scratch`` (V,Hraw,Wraw) uint8 holds the
+        dilated raw mask (allocated here when a mask is dilated and none is given)."""
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3 or not img.is_contiguous():
+            raise EnerfError(f"ingest_raw_u8: img must be a contiguous uint8 (V,Hraw,Wraw,3) tensor, got {img.dtype} {tuple(img.shape)}")
+        V, Hraw, Wraw, _ = img.shape
+        dev = img.device
+        for name, t, shape in (("ixts", ixts, (V, 3, 3)), ("dist", dist, (V, 5))):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+                raise EnerfError(f"ingest_raw_u8: {name} must be a contiguous float32 {shape} tensor on the image's device")
+        if dist is not None and ixts is None:
+            raise EnerfError("ingest_raw_u8: dist needs ixts")
+        for name, t in (("mask", mask), ("scratch", scratch)):
+            if t is not None and (t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != (V, Hraw, Wraw) or not t.is_contiguous()
+                                  or t.device != dev or (name == "scratch" and t.dtype != torch.uint8)):
+                raise EnerfError(f"ingest_raw_u8: {name} must be a contiguous uint8{' / bool' if name == 'mask' else ''} "
+                                 f"({V},{Hraw},{Wraw}) tensor on the image's device")
+        if crop is None:
+            y0, x0 = 0, 0
+            H, W = self.ingest_raw_geometry(Hraw, Wraw, input_ratio)
+        else:
+            y0, x0, H, W = (int(c) for c in crop)
+        if mask is not None and dilate and scratch is None:
+            scratch = torch.empty((V, Hraw, Wraw), dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (V, 3, H, W) or out.device != dev:
+            raise EnerfError(f"ingest_raw_u8: out must be ({V},3,{H},{W}) on the image's device")
+        if mask_out is not None and (mask_out.dtype != torch.uint8 or tuple(mask_out.shape) != (V, H, W) or not mask_out.is_contiguous()
+                                     or mask_out.device != dev):
+            raise EnerfError(f"ingest_raw_u8: mask_out must be a contiguous uint8 ({V},{H},{W}) tensor on the image's device")
+        dp = lambda t: None if t is None else t.data_ptr()
+        self._check(self.dll.enerf_ingest_raw_u8(img.data_ptr(), dp(mask), dp(ixts), dp(dist), V, Hraw, Wraw, float(input_ratio), y0, x0,
+                                                 H, W, int(dilate), dp(scratch), _ptr(out), dp(mask_out), self.stream_of(img)),
+                    "ingest_raw_u8")
         return out
 
     def bounds_near_far(self, vertices, tar_ext, near_min=0.05):

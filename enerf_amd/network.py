@@ -385,15 +385,17 @@ class Network(nn.Module):
         return self._forward(batch, self.options)
 
     # -- source-view cache (enerf_amd/source_cache.py) ----------------------------------------------
-    def cache_sources(self, inps, exts, ixts, masks=None, dilate: int = 0, chunk: int = 0):
+    def cache_sources(self, inps, exts, ixts, masks=None, dilate: int = 0, chunk: int = 0, raw=None):
         """FeatureNet maps, render texels and cameras of the V views a scene / time frame draws its source views from
         (zjumocap/enerf_interactive.py:102-105,138-153), computed once: ``inps`` (V,3,H,W) in [-1,1], ``exts`` (V,4,4),
         ``ixts`` (V,3,3).  ``inps`` may also be the images as a camera or decoder delivers them, (V,H,W,3) uint8, with foreground
         ``masks`` (V,H,W) uint8 and the box size ``dilate`` of their dilation: ``enerf_ingest_views_u8`` then does read_data's
         conversion (:116-124,135,145) on the device.  Eval mode and ``feature_backend="hip"`` only.  ``SourceCache.rebuild`` takes
-        the next time frame in place."""
+        the next time frame in place.  ``raw`` (a :class:`enerf_amd.raw_ingest.RawIngest`): uint8 ``inps`` / ``masks`` are RAW camera
+        frames (V,Hraw,Wraw,3) / (V,Hraw,Wraw), undistorted, resized and cropped on the device (``enerf_ingest_raw_u8``); pass the
+        rig's adjusted intrinsics ``raw.ixts`` as ``ixts``."""
         from .source_cache import SourceCache
-        return SourceCache(self, inps, exts, ixts, chunk, masks, dilate)
+        return SourceCache(self, inps, exts, ixts, chunk, masks, dilate, raw)
 
     def forward_cached(self, cache, view_idx, batch):
         """``forward`` with the source views named by ``view_idx`` — an int32 DEVICE tensor (B,S) or (S,), e.g. the output of

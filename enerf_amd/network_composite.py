@@ -410,13 +410,14 @@ class Network(nn.Module):
         return ret
 
     # -- source-view cache (enerf_amd/composite_cache.py) -------------------------------------------
-    def cache_sources(self, inps, bg_inps, exts, ixts, chunk: int = 0):
+    def cache_sources(self, inps, bg_inps, exts, ixts, chunk: int = 0, raw=None):
         """What both FeatureNets make of the V views a time frame draws its source views from, the render texels (the
         foreground's coloured by ``inps``, the background's by ``bg_inps``) and the cameras, computed once: ``inps`` / ``bg_inps``
         (V,3,H,W) float32 in [-1,1] or (V,H,W,3) uint8, ``exts`` (V,4,4), ``ixts`` (V,3,3).  Eval mode only.
-        ``CompositeSourceCache.rebuild`` takes the next time frame in place."""
+        ``CompositeSourceCache.rebuild`` takes the next time frame in place.  ``raw`` (a :class:`enerf_amd.raw_ingest.RawIngest`):
+        uint8 images are RAW camera frames (V,Hraw,Wraw,3), undistorted, resized and cropped on the device; ``ixts`` = ``raw.ixts``."""
         from .composite_cache import CompositeSourceCache
-        return CompositeSourceCache(self, inps, bg_inps, exts, ixts, chunk)
+        return CompositeSourceCache(self, inps, bg_inps, exts, ixts, chunk, raw)
 
     def forward_cached(self, cache, view_idx, batch):
         """``forward`` with the source views named by ``view_idx`` — an int32 DEVICE tensor (S,) or (1,S), e.g. the output of

@@ -22,6 +22,10 @@ The one place the host can wait is the player's own pinned staging buffer: a hos
 by the CPU, so if the upload that used that buffer ``slots`` submissions ago is still in flight (the host has run that far ahead
 of the device) ``submit`` waits for that upload — never for a kernel.  Device tensors are never staged through the host.
 
+With ``raw=`` (a :class:`enerf_amd.raw_ingest.RawIngest`) the frames submitted are RAW camera frames, (V,Hraw,Wraw,3) uint8 with masks
+(V,Hraw,Wraw): the staging and the device uint8 buffers take the raw size, ``enerf_ingest_raw_u8`` undistorts, resizes and crops them into
+the float image, and ``ixts`` are the rig's adjusted intrinsics (``raw.ixts``); H and W stay the cache's.
+
 Every buffer — pinned staging, device uint8 image and mask, the float image, the build workspace and the caches — is allocated in
 the constructor, so nothing is allocated on one stream and freed under another while a sequence plays.
 """
@@ -53,22 +57,27 @@ class SequencePlayer:
     ``render(view_idx, tar)``  ``Network.forward_cached`` on the front slot, on the caller's current stream.
     """
 
-    def __init__(self, net, exts: torch.Tensor, ixts: torch.Tensor, H: int, W: int, slots: int = 2, dilate: int = 0):
+    def __init__(self, net, exts: torch.Tensor, ixts: torch.Tensor, H: int, W: int, slots: int = 2, dilate: int = 0, raw=None):
         if slots < 2:
             raise ValueError("SequencePlayer: slots must be at least 2 (one to render from, one to build into)")
         if exts.dim() != 3 or exts.device != ixts.device:
             raise ValueError("SequencePlayer: exts (V,4,4) and ixts (V,3,3) on one device")
         self.net, self.H, self.W, self.V, self.dilate = net, int(H), int(W), exts.shape[0], int(dilate)
         self.device = dev = exts.device
+        self.raw = raw
+        if raw is not None and (raw.H, raw.W, raw.V) != (self.H, self.W, self.V):
+            raise ValueError(f"SequencePlayer: raw= gives {raw.V} views of {raw.H}x{raw.W}, the player was opened for {self.V} of {H}x{W}")
+        Hin, Win = (self.H, self.W) if raw is None else (raw.Hraw, raw.Wraw)    # what submit takes and the staging holds
         V, cuda = self.V, exts.is_cuda
         net.prepare()                                       # weight images packed before the two streams start sharing them
         self.build_stream = torch.cuda.Stream(dev) if cuda else None
         exts, ixts = exts.contiguous(), ixts.contiguous()
         pin = (lambda *shape: torch.empty(shape, dtype=torch.uint8, pin_memory=True)) if cuda else (lambda *shape: None)
-        self.slots = [_Slot(SourceCache.empty(net, V, H, W, exts, ixts), pin(V, H, W, 3), pin(V, H, W)) for _ in range(slots)]
+        self.slots = [_Slot(SourceCache.empty(net, V, H, W, exts, ixts), pin(V, Hin, Win, 3), pin(V, Hin, Win)) for _ in range(slots)]
         # the build stream serialises every build, so one device copy of the uint8 frame, one float image and one workspace serve all slots
-        self._img_u8 = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
-        self._mask_u8 = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+        self._img_u8 = torch.empty((V, Hin, Win, 3), dtype=torch.uint8, device=dev)
+        self._mask_u8 = torch.empty((V, Hin, Win), dtype=torch.uint8, device=dev)
+        self._mask_scratch = None if raw is None or not self.dilate else torch.empty((V, Hin, Win), dtype=torch.uint8, device=dev)
         self._image = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
         self._workspace = net.lib.source_cache_build_workspace(H, W, dev)
         self._front = None
@@ -84,14 +93,15 @@ class SequencePlayer:
 
     def nbytes(self) -> int:
         """Device bytes the player holds (caches, uint8 frame + mask, float image, build workspace); ``pinned_nbytes`` is the host's."""
-        own = sum(t.numel() * t.element_size() for t in (self._img_u8, self._mask_u8, self._image, self._workspace))
+        own = sum(t.numel() * t.element_size() for t in (self._img_u8, self._mask_u8, self._image, self._workspace, self._mask_scratch)
+                  if t is not None)
         return own + sum(s.cache.nbytes() for s in self.slots)
 
     def pinned_nbytes(self) -> int:
         return sum(t.numel() for s in self.slots for t in (s.pin_img, s.pin_mask) if t is not None)
 
     def _check_frame(self, frame, masks):
-        V, H, W = self.V, self.H, self.W
+        V, H, W = (self.V, self.H, self.W) if self.raw is None else (self.V, self.raw.Hraw, self.raw.Wraw)
         if frame.dtype != torch.uint8 or tuple(frame.shape) != (V, H, W, 3):
             raise ValueError(f"SequencePlayer.submit: frame must be uint8 ({V},{H},{W},3), got {frame.dtype} {tuple(frame.shape)}")
         if masks is not None and (masks.dtype not in (torch.uint8, torch.bool) or tuple(masks.shape) != (V, H, W)):
@@ -152,7 +162,11 @@ class SequencePlayer:
 
     def _build(self, slot, masked):
         with torch.no_grad():
-            self.net.lib.ingest_views_u8(self._img_u8, self._mask_u8 if masked else None, self.dilate if masked else 0, out=self._image)
+            if self.raw is not None:
+                self.raw(self._img_u8, self._mask_u8 if masked else None, self.dilate if masked else 0, out=self._image, lib=self.net.lib,
+                         scratch=self._mask_scratch)
+            else:
+                self.net.lib.ingest_views_u8(self._img_u8, self._mask_u8 if masked else None, self.dilate if masked else 0, out=self._image)
             slot.cache.rebuild(self._image, workspace=self._workspace)
 
     def flip(self):

@@ -9,6 +9,7 @@ re-running the FeatureNet (``enerf_forward_cached``) — bit-identical to ``Netw
     cache = net.cache_sources(inps, exts, ixts)              # once per time frame: (V,3,H,W), (V,4,4), (V,3,3)
     cache = net.cache_sources(u8, exts, ixts, masks, dilate=5)  # ... or (V,H,W,3) uint8 + (V,H,W) masks, ingested on the device
     cache.rebuild(next_u8, masks=next_masks, dilate=5)       # the next time frame, in place (enerf_amd/sequence.py overlaps it)
+    cache = net.cache_sources(raw_u8, exts, rig.ixts, raw_masks, dilate=5, raw=rig)   # raw camera frames: enerf_amd/raw_ingest.py
     idx = lib.select_views(cam_points, c2w, S)               # per camera, on the device
     out = net.forward_cached(cache, idx, {"tar_ext": ..., "tar_ixt": ..., "near_far": ...})
 """
@@ -27,9 +28,14 @@ class SourceCache:
 
     ``inps`` is either the float image the reference's dataset keeps, (V,3,H,W) float32 in [-1,1], or what a camera / decoder
     delivers, (V,H,W,3) uint8 with optional foreground ``masks`` (V,H,W) uint8 / bool: that one goes through
-    ``enerf_ingest_views_u8`` first (``dilate``: the box size of the mask dilation, 0 or odd 3..9)."""
+    ``enerf_ingest_views_u8`` first (``dilate``: the box size of the mask dilation, 0 or odd 3..9).  With ``raw`` (a
+    :class:`enerf_amd.raw_ingest.RawIngest`) uint8 input is the RAW frame, (V,Hraw,Wraw,3) with masks (V,Hraw,Wraw): it is
+    undistorted, resized and cropped by ``enerf_ingest_raw_u8``, the cache's H and W are the rig's, and ``ixts`` are the rig's
+    adjusted intrinsics (``raw.ixts``)."""
 
-    def __init__(self, net, inps: torch.Tensor, exts: torch.Tensor, ixts: torch.Tensor, chunk: int = 0, masks=None, dilate: int = 0):
+    def __init__(self, net, inps: torch.Tensor, exts: torch.Tensor, ixts: torch.Tensor, chunk: int = 0, masks=None, dilate: int = 0,
+                 raw=None):
+        self._raw = raw
         V, H, W = self._image_shape(inps)
         self._allocate(net, V, H, W, exts, ixts, chunk)
         self.rebuild(inps, masks=masks, dilate=dilate)
@@ -39,11 +45,14 @@ class SourceCache:
         """The buffers of a cache for V views of HxW with nothing in them yet: :meth:`rebuild` fills them (``packed_gen`` is -1
         until then, so ``forward_cached`` refuses the empty cache)."""
         self = cls.__new__(cls)
+        self._raw = None
         self._allocate(net, V, H, W, exts, ixts, chunk)
         return self
 
-    @staticmethod
-    def _image_shape(inps):
+    def _image_shape(self, inps):
+        if self._raw is not None and inps.dtype == torch.uint8:
+            self._raw.check_frame(inps, what="cache_sources (raw)")
+            return inps.shape[0], self._raw.H, self._raw.W
         if inps.dim() == 4 and inps.dtype == torch.uint8 and inps.shape[3] == 3:
             return inps.shape[0], inps.shape[1], inps.shape[2]
         if inps.dim() != 4 or inps.shape[1] != 3 or inps.dtype == torch.uint8:
@@ -101,7 +110,9 @@ class SourceCache:
             self._cams = (exts.contiguous(), ixts.contiguous())
         lib = net.lib
         with torch.no_grad():
-            if inps.dtype == torch.uint8:
+            if inps.dtype == torch.uint8 and self._raw is not None:
+                inps = self._raw(inps, masks, dilate, out=image, lib=lib)
+            elif inps.dtype == torch.uint8:
                 inps = lib.ingest_views_u8(inps.contiguous(), masks, dilate, out=image)
             elif masks is not None or dilate:
                 raise ValueError("cache_sources: masks / dilate belong to uint8 (V,H,W,3) images; a float image is taken as it is")

@@ -807,6 +807,33 @@ int enerf_ingest_views_u8(const unsigned char* img, const unsigned char* mask, i
 int enerf_bounds_near_far(const float* vertices, int n, const float* tar_ext, int B, float near_min, float* near_far,
                           enerf_stream_t stream);
 
+/* ---- raw camera frames (ABI v11 grew by these two entries; new symbols only, the version number is unchanged) ----
+ * What the datasets do on the host in front of the network (zjumocap/enerf_interactive.py:116-135, zjumocap/enerf.py:141-149,
+ * enerf_outdoor/enerf.py:129-152): undistort, resize by input_ratio, dilate / zero by the mask, crop.
+ *   enerf_ingest_raw_u8   img (V,Hraw,Wraw,3) uint8, mask (V,Hraw,Wraw) uint8 or NULL, ixts (V,3,3) and dist (V,5) = (k1,k2,p1,p2,k3)
+ *       float32 on the device -> out (V,3,H,W) float32 in [-1,1] and, unless NULL, mask_out (V,H,W) uint8 0 / 1 (the mask read_data
+ *       returns).  x = (float)u8 / 255.f; keep_raw = mask != 0 dilated as enerf_ingest_views_u8 does (dilate > 0 with a mask: into
+ *       mask_scratch (V,Hraw,Wraw) uint8, a launch of its own in front).  Undistort: the inverse map of cv2.undistort with the new camera
+ *       matrix equal to K — (u,v) samples the raw image at a = (u-cx)/fx, b = (v-cy)/fy, r2 = a*a+b*b, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *       u' = fx (a rad + 2 p1 a b + p2 (r2 + 2 a a)) + cx, v' = fy (b rad + p1 (r2 + 2 b b) + 2 p2 a b) + cy — bilinear, taps outside the
+ *       raw image contribute 0; the undistorted mask is kept where the weight of its kept taps is >= 0.5.  Resize: Hs x Ws as
+ *       enerf_ingest_raw_geometry gives them, s = 1 / input_ratio; output pixel d of an axis averages the undistorted pixels j with
+ *       weight |[d s, (d+1) s) n [j, j+1) n [0, src)| normalised to 1, separably (INTER_AREA; the 2x2 mean at 0.5 on even sizes); the
+ *       mask takes j = min(floor(d s), src - 1) (INTER_NEAREST).  Then the crop (crop_y, crop_x, H, W) of the resized image,
+ *       x = 0 where !keep, out = 2x - 1: a masked-out or out-of-image pixel is exactly -1.  Coordinates and weights are double, pixel
+ *       values and their sums float32: within (2 (9 + n) + 1) 2^-24 of the float64 evaluation, n = undistorted pixels under an output
+ *       pixel.  dist NULL: no bilinear step at all (ixts is then not read and may be NULL); with input_ratio 1 and no crop the result is
+ *       enerf_ingest_views_u8's bit for bit.  A zero dist tensor still takes the bilinear path.  Whatever ixts and dist hold (NaN, inf,
+ *       fx = 0), no address outside the raw image is formed: such pixels are -1.  NOT cv2's bits: its map is rounded to 1/32 pixel, it
+ *       drops area overlaps under 1e-3 pixel and sums in another order.  No readback; graph-capturable.
+ *       ENERF_EINVAL, nothing launched: NULL img / out, V < 1, input_ratio outside [0.25, 1], a crop that leaves the resized image,
+ *       dilate not 0 or odd 3..9, dilate > 0 with a mask but no mask_scratch, mask_out without a mask, dist without ixts.
+ *   enerf_ingest_raw_geometry   host only: *Hs, *Ws = Hraw input_ratio, Wraw input_ratio rounded half-to-even. */
+int enerf_ingest_raw_u8(const unsigned char* img, const unsigned char* mask, const float* ixts, const float* dist, int V, int Hraw,
+                        int Wraw, double input_ratio, int crop_y, int crop_x, int H, int W, int dilate, unsigned char* mask_scratch,
+                        float* out, unsigned char* mask_out, enerf_stream_t stream);
+int enerf_ingest_raw_geometry(int Hraw, int Wraw, double input_ratio, int* Hs, int* Ws);
+
 /* ---- the composite network (network_composite.py: boxed foreground layers over a background; ABI v11 grew by these five entries;
  * new symbols only, the version number is unchanged).  B == 1 wherever a window's rays are selected, as in the reference, which
  * reads batch['bbox'][0] for every batch element.  A window is (x0, y0, ww, wh) in pixels of the grid it is cut from.
