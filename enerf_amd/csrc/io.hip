@@ -696,3 +696,5 @@ void launch_eval_ssim(const float* pred_rgb, const float* gt_rgb, const void* ma
 #include "perceptual_vgg.h"
 // Raw camera frames (undistort, area resize, crop) to the float image of the source-view caches (enerf_outdoor/enerf.py:129-152)
 #include "ingest_raw.h"
+// The foreground's world-space box of a time frame, carved from the masks (the reference loads it from vhull/*.npy made offline)
+#include "vhull.h"

@@ -183,6 +183,15 @@ class CompositeCacheStruct(C.Structure):
 
 
 COMPOSITE_CACHE_BUFFERS = 4 * MAX_LEVELS + 2
+VHULL_MAX_VIEWS = 64
+
+
+class VhullArgs(C.Structure):
+    """``enerf_vhull_t``."""
+    _fields_ = ([("masks", C.c_void_p), ("exts", _f), ("ixts", _f)] + [(n, _i) for n in ("V", "H", "W")]
+                + [("scene_bounds", (_fl * 3) * 2), ("grid", _i * 3)] + [(n, _i) for n in ("n_layers", "labels", "min_views", "max_miss")]
+                + [("pad", C.c_double), ("bounds", _f), ("counts", C.c_void_p), ("flags", C.c_void_p), ("corners", _f),
+                   ("occupancy", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)])
 
 
 class _ConvWB(C.Structure):
@@ -376,6 +385,8 @@ _SIGNATURES = {
     "enerf_forward_composite_cached_moving_workspace_bytes": (C.c_size_t, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct)]),
     "enerf_forward_composite_cached_moving": (_i, [C.POINTER(CompositeFrameArgs), C.POINTER(CompositeCacheStruct), C.c_void_p, _f,
                                                    C.c_void_p, _f]),
+    "enerf_vhull_workspace_bytes": (C.c_size_t, [C.POINTER(VhullArgs)]),
+    "enerf_vhull_bounds": (_i, [C.POINTER(VhullArgs), _f]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1759,6 +1770,68 @@ class EnerfLib:
         self._check(self.dll.enerf_ingest_raw_u8(img.data_ptr(), dp(mask), dp(ixts), dp(dist), V, Hraw, Wraw, float(input_ratio), y0, x0,
                                                  H, W, int(dilate), dp(scratch), _ptr(out), dp(mask_out), self.stream_of(img)),
                     "ingest_raw_u8")
+        return out
+
+    def vhull_workspace(self, n_layers=1, device="cpu"):
+        """The accumulators of one ``vhull_bounds`` call in flight: ``enerf_vhull_workspace_bytes`` bytes as an int32 tensor."""
+        a = VhullArgs(n_layers=int(n_layers))
+        n = self.dll.enerf_vhull_workspace_bytes(C.byref(a))
+        if n == 0:
+            raise EnerfError(f"vhull_workspace failed: {self.dll.enerf_last_error().decode()}")
+        return torch.empty(((n + 3) // 4,), dtype=torch.int32, device=device)
+
+    def vhull_bounds(self, masks, exts, ixts, scene_bounds, grid=(128, 128, 128), n_layers=1, labels=False, min_views=2, max_miss=0,
+                     pad=0.0, out=None, occupancy=None, workspace=None):
+        """The foreground's world-space box per layer, carved from the masks (the model: include/enerf_hip.h, enerf_vhull_bounds):
+        masks (V,H,W) uint8 / bool, exts (V,4,4) and ixts (V,3,3) float32 at the masks' resolution, all on one device;
+        ``scene_bounds`` ((lo), (hi)) and ``grid`` (Gx,Gy,Gz) are HOST values (a sequence, an array or a CPU tensor).  Returns
+        ``(bounds (L,2,3) float32, counts (L) int32, flags (L) int32, corners (L,8,3) float32)`` — ``out`` when given, the same four.
+        ``occupancy`` (Gz,Gy,Gx) uint8 receives the voxels (bit l = layer l).  ``workspace``: :meth:`vhull_workspace`, the caller's
+        own for calls on a stream of its own or under graph capture (allocated here otherwise).  Nothing is read back."""
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        if masks.dtype != torch.uint8 or masks.dim() != 3 or not masks.is_contiguous():
+            raise EnerfError(f"vhull_bounds: masks must be a contiguous uint8 / bool (V,H,W) tensor, got {masks.dtype} {tuple(masks.shape)}")
+        V, H, W = masks.shape
+        dev = masks.device
+        for name, t, shape in (("exts", exts, (V, 4, 4)), ("ixts", ixts, (V, 3, 3))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise EnerfError(f"vhull_bounds: {name} must be a contiguous float32 {shape} tensor on the masks' device")
+        if isinstance(scene_bounds, torch.Tensor) and scene_bounds.device.type != "cpu":
+            raise EnerfError("vhull_bounds: scene_bounds are host values (part of the plan), got a device tensor")
+        sb = torch.as_tensor(scene_bounds, dtype=torch.float32).reshape(-1).tolist()
+        grid = tuple(int(x) for x in grid)
+        if len(sb) != 6 or len(grid) != 3:
+            raise EnerfError("vhull_bounds: scene_bounds is ((x0,y0,z0),(x1,y1,z1)) and grid (Gx,Gy,Gz)")
+        L = int(n_layers)
+        shapes = ((L, 2, 3), (L,), (L,), (L, 8, 3))
+        dtypes = (torch.float32, torch.int32, torch.int32, torch.float32)
+        if out is None:
+            out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+        else:
+            out = tuple(out)
+            names = ("bounds", "counts", "flags", "corners")
+            if len(out) != 4:
+                raise EnerfError("vhull_bounds: out is (bounds, counts, flags, corners)")
+            for name, t, s, d in zip(names, out, shapes, dtypes):
+                if tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() or t.device != dev:
+                    raise EnerfError(f"vhull_bounds: out {name} must be a contiguous {d} {s} tensor on the masks' device")
+        if occupancy is not None and (occupancy.dtype != torch.uint8 or tuple(occupancy.shape) != grid[::-1] or not occupancy.is_contiguous()
+                                      or occupancy.device != dev):
+            raise EnerfError(f"vhull_bounds: occupancy must be a contiguous uint8 {grid[::-1]} tensor on the masks' device")
+        if workspace is None:
+            workspace = self.vhull_workspace(L, dev)
+        elif workspace.device != dev or not workspace.is_contiguous():
+            raise EnerfError("vhull_bounds: workspace must be a contiguous tensor on the masks' device")
+        a = VhullArgs(masks=masks.data_ptr(), exts=exts.data_ptr(), ixts=ixts.data_ptr(), V=V, H=H, W=W, n_layers=L, labels=int(bool(labels)),
+                      min_views=int(min_views), max_miss=int(max_miss), pad=float(pad), bounds=out[0].data_ptr(), counts=out[1].data_ptr(),
+                      flags=out[2].data_ptr(), corners=out[3].data_ptr(), occupancy=None if occupancy is None else occupancy.data_ptr(),
+                      workspace=workspace.data_ptr(), workspace_bytes=workspace.numel() * workspace.element_size())
+        for i in range(6):
+            a.scene_bounds[i // 3][i % 3] = sb[i]
+        for i in range(3):
+            a.grid[i] = grid[i]
+        self._check(self.dll.enerf_vhull_bounds(C.byref(a), self.stream_of(masks)), "vhull_bounds")
         return out
 
     def bounds_near_far(self, vertices, tar_ext, near_min=0.05):

@@ -1103,6 +1103,65 @@ size_t enerf_forward_composite_cached_moving_workspace_bytes(const enerf_composi
 int enerf_forward_composite_cached_moving(const enerf_composite_frame_args_t* args, const enerf_composite_cache_t* cache,
                                           const int* view_idx, const float* bbox_xy, int* flags, enerf_stream_t stream);
 
+/* ---- foreground bounds from the masks: a visual-hull box per time frame (ABI v11 grew by these two entries; new symbols only, the
+ * version number is unchanged).  The reference loads this box from files another tool made (enerf_outdoor/enerf.py:64 and
+ * enerf_path.py:65 read vhull/{frame:06d}.npy; zjumocap reads fitted SMPL vertices) and holds no program that makes it, so the model
+ * below is the specification.  Every coordinate is double.
+ *
+ *   Inputs.  masks (V,H,W) uint8; exts (V,4,4) world -> camera and ixts (V,3,3), float32, at the masks' resolution (for a raw rig:
+ *       the rig's adjusted intrinsics); scene_bounds = (lo, hi) with lo < hi on every axis; the grid (Gx,Gy,Gz), each in 1..256;
+ *       n_layers L in 1..ENERF_MAX_FG_LAYERS; labels 0 / 1; min_views >= 1; max_miss >= 0; pad >= 0 in world units.  All but the
+ *       three tensors are host values: they are part of the plan.
+ *   Voxel and projection.  Voxel (i,j,k) has the centre p = lo + (idx + 0.5) * (hi - lo) / G on every axis.  For view v,
+ *       c = R p + t (rows 0..2 of ext).  The view ABSTAINS on the voxel if !(c.z > 0) (NaN included).  Else u = K[0] c.x / c.z + K[2]
+ *       and v = K[4] c.y / c.z + K[5] — K[1], the skew, is not read — and iu = floor(u + 0.5), iv = floor(v + 0.5).  The view also
+ *       abstains if !(iu >= 0 && iu < W && iv >= 0 && iv < H), tested in double BEFORE any conversion to an integer: no camera, not
+ *       even one holding NaN, inf or fx = 0, can form an address outside a mask.
+ *   Voting.  Else m = masks[v,iv,iu].  With labels the view votes INSIDE for layer l iff m == l + 1; without labels (L must be 1)
+ *       iff m != 0.  Any other outcome is a vote OUTSIDE.  Voxel occupied for layer l <=> inside_l >= min_views && outside_l <= max_miss.
+ *   Outputs per layer, with imin..imax the occupied index range of an axis and cell = (hi - lo) / G:
+ *       bounds (L,2,3) float32 = (lo + imin cell - pad, lo + (imax + 1) cell + pad), evaluated in double in that order (no fused
+ *           multiply-add) and rounded once to float32;
+ *       counts (L) int32 = occupied voxels;
+ *       flags (L) int32: bit 0 = nothing occupied, bounds[l] is then scene_bounds exactly (no pad); bit 1 = the occupied range touches
+ *           a face of the grid, so the scene box clips the hull;
+ *       corners (L,8,3) float32 = the eight corners of bounds[l] in base_utils.get_bound_corners' order (corner c takes its x from
+ *           the max corner iff bit 2 of c is set, y by bit 1, z by bit 0): the `vertices` enerf_bounds_near_far takes;
+ *       occupancy (Gz,Gy,Gx) uint8, bit l = layer l occupied; NULL = not written.
+ *   The result is a function of the inputs alone: the reductions are integer (min, max, add), so the order of the blocks cannot show
+ *   and two calls give the same bits.  A voxel whose u + 0.5 or v + 0.5 lies within rounding of an integer may fall either way against
+ *   another evaluation of the same model.
+ *
+ *   enerf_vhull_bounds   only enqueues (no synchronisation, no allocation, graph-capturable): a fill kernel that clears the
+ *       accumulators in `workspace`, the carving kernel, a one-block finish.  The clearing is part of the enqueued work, so neither the
+ *       workspace's earlier contents nor an earlier replay can show.  workspace: enerf_vhull_workspace_bytes(args) bytes, 4-byte aligned,
+ *       owned by the call until the stream has run it.
+ *       ENERF_EINVAL, nothing launched: a null args / masks / exts / ixts / bounds / counts / flags / corners / workspace; V outside
+ *       1..ENERF_VHULL_MAX_VIEWS; H or W outside 1..32768; a grid extent outside 1..256; L outside 1..ENERF_MAX_FG_LAYERS;
+ *       labels == 0 with L > 1; min_views < 1; max_miss < 0; pad negative or not finite; scene_bounds not finite or lo >= hi;
+ *       workspace_bytes too small.
+ *   enerf_vhull_workspace_bytes   host only; 0 + enerf_last_error() on a null args or L outside its range. */
+#define ENERF_VHULL_MAX_VIEWS 64
+typedef struct {
+    const unsigned char* masks;                /* (V,H,W) */
+    const float* exts;                         /* (V,4,4) */
+    const float* ixts;                         /* (V,3,3) */
+    int V, H, W;
+    float scene_bounds[2][3];                  /* lo, hi */
+    int grid[3];                               /* Gx, Gy, Gz */
+    int n_layers, labels, min_views, max_miss;
+    double pad;
+    float* bounds;                             /* (L,2,3) */
+    int* counts;                               /* (L) */
+    int* flags;                                /* (L) */
+    float* corners;                            /* (L,8,3) */
+    unsigned char* occupancy;                  /* (Gz,Gy,Gx) or NULL */
+    void* workspace;
+    size_t workspace_bytes;
+} enerf_vhull_t;
+size_t enerf_vhull_workspace_bytes(const enerf_vhull_t* args);
+int enerf_vhull_bounds(const enerf_vhull_t* args, enerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
